@@ -6,12 +6,13 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-A "step" is one PhantomEnv.step() of every env instance of the batch.  The timed region runs the
-K-step region R times back to back (R chosen so that it lasts >= 1 s; printed as "repeats") as
-fused on-device rollouts (phx_rollout, T=400 = four episodes per launch by default; every step's observation,
-action, reward and done flags are written to the trajectory buffer in HBM) with inputs/state
+A "step" is one PhantomEnv.step() of every env instance of the batch.  The timed region is exactly K
+steps, run as fused on-device rollouts (phx_rollout, 8 fragments of 100 steps per call by default; every step's
+observation, action, reward and done flags are written to the trajectory buffer in HBM) with inputs/state
 already resident in HBM, bracketed by barrier + synchronize, max over ranks.
-value = A * B_total * R * K / time  (agent-steps/s, whole job); ms_per_step = time / (R * K).
+value = A * B_total * K / time  (agent-steps/s, whole job); ms_per_step = time / K.
+`--dump-outputs DIR` writes what the timed path returned for its last step as DIR/<name>.npy; the inputs (seed,
+device-RNG actions and orders, the steps taken before the timed region) depend on the arguments only.
 The launches rotate over >= 4 trajectory buffers (> 256 MB in total, more than the Infinity Cache holds) so that the
 written bytes really reach HBM.  `--gpus N` without a torchrun environment re-executes itself under
 torch.distributed.run.  The per-launch PhantomEnv.step mode (one kernel per step) is measured right after and
@@ -372,6 +373,28 @@ def other_configs(device):
     return res
 
 
+def dump_outputs(out_dir, frag, t, limit=64 << 20):
+    """What the timed path hands its caller for the LAST timed step, as float32 DIR/<name>.npy: row t of the trajectory
+    fragment that holds it (observations, actions, rewards, truncations, terminations) and the observation after it
+    (last_obs).  Over `limit` bytes in all, a fixed seeded sample of env rows is written instead, with their indices
+    (env_index.npy)."""
+    planes = {"observations": frag.observations[t], "actions": frag.actions[t], "rewards": frag.rewards[t],
+              "truncations": frag.truncations[t], "last_obs": frag.last_obs}
+    if frag.terminations is not None:
+        planes["terminations"] = frag.terminations[t]
+    B = frag.observations.shape[1]
+    per_env = sum(x[0].numel() for x in planes.values()) * 4
+    rows = None
+    if per_env * B > limit:
+        rows = np.sort(np.random.RandomState(0).choice(B, (limit - 4096) // (per_env + 8), replace=False))    # 4 KB: the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in planes.items():
+        a = x.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if rows is None else a[rows])
+    if rows is not None:
+        np.save(os.path.join(out_dir, "env_index.npy"), rows.astype(np.float64))
+
+
 def _free_port():
     import socket
     with socket.socket() as so:
@@ -476,8 +499,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1000)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="sc64")
     ap.add_argument("--batch", type=int, default=None, help="envs per GPU (default: the config's)")
-    ap.add_argument("--min-region-ms", type=float, default=6000.0,
-                    help="the K-step region is repeated back to back until the timed region lasts at least this long")
+    ap.add_argument("--min-region-ms", type=float, default=None,
+                    help="ignored: the timed region is exactly --steps steps (accepted so that older command lines still run)")
     ap.add_argument("--buffers", type=int, default=0,
                     help="trajectory buffers the launches rotate over (default: enough for > 320 MB, at least 4)")
     ap.add_argument("--episodes-per-launch", type=int, default=1,
@@ -486,6 +509,8 @@ def main():
                     help="fragments per phx_rollout call (phx_rollout_io.frags, ABI 9): the consumer gets one-episode fragments in separate "
                          "buffers, the pipeline fill, the placement of a 160 KB workgroup on every CU and the kernel boundary are paid once "
                          "per call (round 4: ONE four-episode fragment per launch = --episodes-per-launch 4 --fragments-per-call 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last step to DIR/<name>.npy (float32; rank 0's envs)")
     ap.add_argument("--no-autotune", action="store_true", help="keep the library's default block shape (no env.autotune_rollout)")
     ap.add_argument("--watchdog-s", type=float, default=900.0, help="overall deadline; a JSON line with `error` is printed when it passes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -617,37 +642,51 @@ def run(args, rank, local_rank, world, watch):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    # The env steps as a continuous stream (auto-reset at every episode end), issued as fragments of T = 100
-    # steps per launch.  A K-step region shorter than ~1 s would time launch + sync latency, not the path
-    # (K = 20 is ONE 8 us slice) and the driver's GPU-busy sampler would see an idle chip: the region is therefore
-    # repeated R times back to back, R the smallest
-    # count that makes R*K a whole number of fragments and the timed region >= --min-region-ms; the line
-    # reports steps = K, repeats = R and ms_per_step = elapsed / (R*K).  Warm-up: W steps rounded up to whole
-    # fragments (at least 20 fragments, which also calibrates R -- identically on every rank).
-    import math
-    watch.stage("warm-up + calibration", 240)
+    # The env steps as a continuous stream (auto-reset at every episode end), issued as calls of NF fragments of TF steps.
+    # The timed region is exactly K steps: q = K // T full calls, then the r = K % T steps left as one call of r // TF
+    # fragments (the next buffer set of the rotation) and one call of r % TF steps into a buffer of its own.  A small K
+    # times launch + sync latency rather than the path; ms_per_step = elapsed / K tells the caller how many steps make a
+    # region of the length it wants.  Warm-up: W steps rounded up to whole calls (at least 20), then 200 more calls that
+    # size the timed stage's deadline.  The number of steps before the timed region depends on the arguments only, so
+    # the same arguments step the same inputs.
+    watch.stage("warm-up", 240)
     n_warm = max(20, -(-W // T))
     launches(n_warm)
     sync_barrier()
     t0 = time.perf_counter(); launches(200); torch.cuda.synchronize()
     per_launch = max_over_ranks((time.perf_counter() - t0) / 200)
-    unit = T // math.gcd(K, T)                              # repeats per whole number of fragments
-    R = max(1, math.ceil(1.05 * args.min_region_ms * 1e-3 / per_launch * T / K))
-    R = -(-R // unit) * unit
-    n_launch = R * K // T
-    watch.stage("timed region", 120 + 20 * args.min_region_ms * 1e-3)
+    q, r = divmod(K, T)
+    f_rest, g_rest = divmod(r, TF)
+    tail = dev.alloc_trajectory(g_rest) if g_rest else None
+
+    def timed_steps():
+        """the K timed steps; returns the fragment that holds the last of them"""
+        launches(q)
+        last = trajs[(rot[0] - 1) % len(trajs)][-1] if q else None
+        if f_rest:
+            last = dev.rollout_fragments(TF, trajs[rot[0] % len(trajs)][:f_rest])[-1]
+            rot[0] += 1
+        if g_rest:
+            last = dev.rollout(g_rest, out=tail)
+        return last
+
+    n_launch = q + (f_rest > 0) + (g_rest > 0)
+    watch.stage("timed region", 120 + 20 * per_launch * (K / T + 2))
     sync_barrier()
     t0 = time.perf_counter()
-    launches(n_launch)
-    torch.cuda.synchronize()                 # this rank's R*K steps are done ...
+    last_frag = timed_steps()
+    torch.cuda.synchronize()                 # this rank's K steps are done ...
     elapsed = time.perf_counter() - t0
     sync_barrier()                           # ... all ranks are; the job's time is the MAX over ranks
     elapsed = max_over_ranks(elapsed)
-    value = N_AGENTS * B * world * (R * K) / elapsed
+    if args.dump_outputs and rank == 0:
+        watch.stage("dump outputs", 120)
+        dump_outputs(args.dump_outputs, last_frag, g_rest - 1 if g_rest else TF - 1)
+    value = N_AGENTS * B * world * K / elapsed
     out = watch.line
     out.update({
         "metric": "agent_steps_per_sec", "value": value, "unit": "agent-steps/s",
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / (R * K) * 1e3,
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "i32", "data": "synthetic",
         "config": {"workload": f"supply-chain {args.config.upper()} (1 factory + {N_SHOPS} shops + "
@@ -664,11 +703,12 @@ def run(args, rank, local_rank, world, watch):
                                     ("every word stored by the kernel's store waves, whole 16-byte pieces (no fill launch)" if store_waves
                                      else "every word stored by the kernel"))),
                    "served_by": served_by},
-        "repeats": R, "timed_steps": R * K, "timed_launches": n_launch, "timed_region_ms": elapsed * 1e3,
-        "warmup_launches": n_warm,
-        "timing_note": f"the {K}-step region is run {R}x back to back as {n_launch} calls of {NF} x {TF} steps; "
-                       "ms_per_step = timed_region_ms / (repeats * steps)",
-        "env_steps_per_sec": B * world * (R * K) / elapsed,
+        "timed_steps": K, "timed_launches": n_launch, "timed_region_ms": elapsed * 1e3,
+        "warmup_launches": n_warm + 200,
+        "timing_note": f"the {K} timed steps run as {q} calls of {NF} x {TF} steps"
+                       + (f" + one call of {f_rest} x {TF}" if f_rest else "") + (f" + one call of {g_rest}" if g_rest else "")
+                       + "; ms_per_step = timed_region_ms / steps",
+        "env_steps_per_sec": B * world * K / elapsed,
         "control_plane": "gloo" if dist is not None else None,
     })
 

@@ -38,3 +38,33 @@ def test_error_line_keeps_partial_measurements():
     line = bench.error_line(8, "boom", stage="rollout_allgather", partial={"value": 1.0e12, "rccl_ranks_seen": 8, "steps": 20})
     assert line["value"] == 1.0e12 and line["n_gpus"] == 8 and line["rccl_ranks_seen"] == 8
     assert line["error"] == "boom" and line["failed_stage"] == "rollout_allgather" and line["metric"] == "agent_steps_per_sec"
+
+
+def test_dump_outputs_writes_the_last_step_as_float32_within_the_limit(tmp_path):
+    """--dump-outputs: row t of every plane of the fragment plus last_obs, float32; over the limit a seeded sample of env rows
+    (the same rows every time) and their indices."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from phantom_amd.device import Trajectory
+    T, B, S, D, t = 5, 1000, 9, 3, 3
+    g = torch.Generator().manual_seed(0)
+    tr = Trajectory(torch.randn(T, B, S, D, generator=g), torch.randn(T, B, S, generator=g), torch.randn(T, B, S, generator=g),
+                    torch.zeros(T, B, S, dtype=torch.uint8), (torch.arange(T * B * S) % 3 == 0).to(torch.uint8).view(T, B, S),
+                    torch.randn(B, S, D, generator=g))
+    bench.dump_outputs(str(tmp_path / "full"), tr, t)
+    full = {f[:-4]: np.load(str(tmp_path / "full" / f)) for f in os.listdir(str(tmp_path / "full"))}
+    assert sorted(full) == ["actions", "last_obs", "observations", "rewards", "terminations", "truncations"]
+    assert all(a.dtype == np.float32 for a in full.values())
+    np.testing.assert_array_equal(full["observations"], tr.observations[t].numpy())
+    np.testing.assert_array_equal(full["truncations"], tr.truncations[t].float().numpy())
+    np.testing.assert_array_equal(full["last_obs"], tr.last_obs.numpy())
+    limit = 100_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), tr, t, limit=limit)
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= limit
+    rows = np.load(str(tmp_path / "a" / "env_index.npy")).astype(np.int64)
+    np.testing.assert_array_equal(rows, np.load(str(tmp_path / "b" / "env_index.npy")))
+    assert 0 < len(rows) < B and (np.diff(rows) > 0).all()
+    for name, a in full.items():
+        np.testing.assert_array_equal(np.load(str(tmp_path / "a" / (name + ".npy"))), a[rows])

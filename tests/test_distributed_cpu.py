@@ -15,6 +15,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
+def _cpu_barrier():
+    """a barrier over the gloo group that stays on the CPU: dist.barrier() asks torch for the accelerator, which opens the GPU
+    (where there is one) in every rank of these CPU-only tests"""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, tmp):
     sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -53,7 +59,7 @@ def _worker(rank, world, port, tmp):
         # [C, W, tc, ...] -> [W, C*tc, ...]
         glued = torch.cat([ch[c] for c in range(ch.shape[0])], dim=1)
         assert torch.equal(glued, g)
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -108,7 +114,7 @@ def _worker8(rank, world, port, tmp):
                                   for c in range(col.n_chunks)], dim=0) for r in range(world)])
     if rank == 0:
         np.savez(os.path.join(tmp, "col.npz"), obs=obs.numpy(), tru=tru.numpy())
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 

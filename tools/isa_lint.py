@@ -6,7 +6,7 @@ to ISA (hipcc -S --cuda-device-only, the library's flags), finds each listed ins
 that contains a global store) and counts what must not be there.
     python tools/isa_lint.py            # table + exit status 1 if an instantiation that has to be clean is not
 """
-import os, re, subprocess, sys, tempfile
+import hashlib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "phantom_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -80,7 +80,13 @@ def count(seg):
 def run(verbose=True, only_clean=False):
     """-> (number of instantiations that have to be clean and are not, report text)"""
     from concurrent.futures import ThreadPoolExecutor
-    cache = os.path.join(tempfile.gettempdir(), "phx_isa_lint")
+    # the ISA cache belongs to this user and to these sources: a directory shared by every checkout could hand one tree's
+    # ISA to another, and one user's directory is not writable for the next
+    h = hashlib.sha256(" ".join([HIPCC] + FLAGS[:-4]).encode())
+    for d in (CSRC, os.path.join(ROOT, "include")):
+        for f in sorted(os.listdir(d)):
+            h.update(f.encode() + b"\0" + open(os.path.join(d, f), "rb").read())
+    cache = os.path.join(tempfile.gettempdir(), f"phx_isa_lint_{os.getuid()}_{h.hexdigest()[:16]}")
     os.makedirs(cache, exist_ok=True)
     tables = (("must be clean", CLEAN, True),) + (() if only_clean else (("for information", INFO, False),))
     files = sorted({src for _, t, _ in tables for src, _, _ in t})

@@ -9,7 +9,7 @@
 #      gather included scales at all (DESIGN_HISTORY section 7: ~38 ms ring / ~5.5 ms direct for 0.84 GB per rank, against 0.2 ms of stepping)
 # Every line carries n_gpus, value (whole-job agent-steps/s), rccl_ranks_seen, rccl_env, and in rollout_allgather: ms, recv_GBps_per_rank,
 # per_link_GBps_if_direct.  summary.txt tabulates them.  --dry-run: every rank on the GPUs that exist (PHX_BENCH_SHARE_GPU=1), short regions,
-# N = 1, 2, 8 only: checks the plumbing of this script on a 1-GPU box (tests/test_gpu_round6.py).
+# N = 1, 2, 3 only (three ranks on one GPU at most): checks the plumbing of this script on a 1-GPU box (tests/test_gpu_round6.py).
 set -u
 DRY=0
 if [ "${1:-}" = "--dry-run" ]; then DRY=1; shift; fi
@@ -20,11 +20,11 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0 MASTER_ADDR=127.0.0.1
 PY=${PYTHON:-python}
 if [ $DRY = 1 ]; then
   export PHX_BENCH_SHARE_GPU=1
-  NS="1 2 8"; STAGE_T=${STAGE_TIMEOUT:-420}
-  ARGS="--steps 20 --warmup 5 --min-region-ms 200 --no-cpu-baseline --no-other-configs --no-per-step --no-frag200 --no-autotune --batch 256 --watchdog-s 360"
+  NS="1 2 3"; STAGE_T=${STAGE_TIMEOUT:-420}
+  ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-per-step --no-frag200 --no-autotune --batch 256 --watchdog-s 360"
 else
   NS="1 2 4 8"; STAGE_T=${STAGE_TIMEOUT:-900}
-  ARGS="--steps 2000 --warmup 200 --no-cpu-baseline --no-other-configs --no-per-step --watchdog-s 840"
+  ARGS="--steps 24000000 --warmup 200 --no-cpu-baseline --no-other-configs --no-per-step --watchdog-s 840"
 fi
 stage() {   # name, env assignments (may be empty), n_gpus
   local name=$1 envs=$2 n=$3 port=$((29600 + RANDOM % 300))
