@@ -256,6 +256,9 @@ typedef struct phx_spec {
                                    PHX_VR_AUTO picks where its workgroup shape applies; PHX_VR_TIME_PARALLEL keeps the round-3 kernel.
                                    FSM supply chain (round 5): that kernel's FSM instantiation wherever its plan applies (PHX_VR_AUTO: for
                                    fragments of >= 200 steps on batches above 65 536 (env, shop) pairs) */
+#define PHX_VR_POLICY_MFMA   6  /* a rollout with a device policy (phx_rollout_io.policy): phx_sc_rollout_policy_mfma_kernel also for a ReLU /
+                                   hard-tanh policy of widths <= 64 that phx_sc_rollout_policy_kernel serves by default (tanh and wide policies
+                                   always take it); ignored without a policy                                                                   */
 #define PHX_VB_WHOLE_ENVS   (-1)
 /* phx_spec.variant_step */
 #define PHX_VS_AUTO          0
@@ -361,17 +364,47 @@ typedef struct phx_rollout_frag {
  *     h1[i] = act(c),  c = b[1][i];  for k = 0 .. width[0]-1 ascending: c = fmaf(w[1][i * width[0] + k], h0[k], c)      (n_hidden == 2)
  *     y = b[n_hidden][0];            for k = 0 .. width[last]-1 ascending: y = fmaf(w[n_hidden][k], h[k], y)
  *     a = fmaf(out_scale, y, out_bias);   action = (a < out_lo ? out_lo : (a > out_hi ? out_hi : a)) + 0.0f      (an exact zero is +0)
- *     act = PHX_ACT_RELU: c > 0 ? c : +0;   PHX_ACT_HARD_TANH: c < -1 ? -1 : (c > 1 ? 1 : c)
+ *     act = PHX_ACT_RELU: c > 0 ? c : +0;   PHX_ACT_HARD_TANH: c < -1 ? -1 : (c > 1 ? 1 : c);   PHX_ACT_TANH: below
  * (fmaf = the correctly rounded fused multiply-add of C99 / v_fma_f32: one rounding per term, on every machine).  The layouts are
  * torch.nn.Linear's own (weight [out][in] row-major, bias [out]): the parameters of a module are passed as they are, device pointers,
  * read during the launch.  Weights and observations must be finite.  Served for plain supply-chain envs (ShopAgent observations,
  * D = 3) by phx_sc_rollout_policy_kernel, one lane per (env, shop); out_lo >= 0 (ShopAgent's action space is Box(0, SHOP_MAX_STOCK)).  */
 #define PHX_ACT_RELU      0
 #define PHX_ACT_HARD_TANH 1
+/* ABI 10, additive: PHX_ACT_TANH, an odd rational approximation of tanh made of f32 operations only (every step correctly rounded, so
+ * it is restated bit for bit on any machine; no exp / reciprocal approximations):
+ *     a = |c|;   if !(a < PHX_TANH_SAT): t = 1;   else if a < PHX_TANH_SMALL: t = a;
+ *     else { s = a * a;
+ *            p = PHX_TANH_A13;  p = fmaf(p, s, PHX_TANH_A11);  ...  p = fmaf(p, s, PHX_TANH_A1);     (A13, A11, A9, A7, A5, A3, A1)
+ *            q = PHX_TANH_B6;   q = fmaf(q, s, PHX_TANH_B4);   q = fmaf(q, s, PHX_TANH_B2);   q = fmaf(q, s, PHX_TANH_B0);
+ *            t = (a * p) / q;  t = t > 1 ? 1 : t; }                 (* and / are the correctly rounded f32 multiply and division)
+ *     act(c) = c < 0 || c is -0 ? -t : t                              (the sign of c copied onto t: act(-c) == -act(c) bit for bit)
+ * |act(c)| <= 1, |act(c) - tanh(c)| <= 4e-7 for every finite c, relative error <= 1e-6 for 2^-12 <= |c| <= 1 (checked exhaustively
+ * over a dense grid of bit patterns by tests/test_policy_wide_cpu.py; an odd degree-13 numerator over an even degree-6 denominator).  */
+#define PHX_ACT_TANH      2
+#define PHX_TANH_SAT   0x1.f9f09ep+2f    /* 7.9053111: 1 - tanh(a) < 2.8e-7 above it */
+#define PHX_TANH_SMALL 0x1p-12f          /* tanh(a) = a (1 - a^2 / 3 + ...): below it the identity is within 2e-8 relative */
+#define PHX_TANH_A1    0x1.40b3b8p-8f
+#define PHX_TANH_A3    0x1.4e1bdap-11f
+#define PHX_TANH_A5    0x1.f28694p-17f
+#define PHX_TANH_A7    0x1.b80082p-25f
+#define PHX_TANH_A9   -0x1.7a6ffep-34f
+#define PHX_TANH_A11   0x1.c266fcp-43f
+#define PHX_TANH_A13  -0x1.3e4b80p-52f
+#define PHX_TANH_B0    0x1.40b3bap-8f
+#define PHX_TANH_B2    0x1.29540ap-9f
+#define PHX_TANH_B4    0x1.f12bacp-14f
+#define PHX_TANH_B6    0x1.41a7b0p-20f
+/* hidden widths: 1 .. PHX_POLICY_MAX_WIDTH (64), or (ABI 10, additive) a multiple of PHX_POLICY_WIDE_STEP up to PHX_POLICY_WIDE_MAX
+ * (96, 128, ..., 256: RLlib's default fcnet_hiddens = [256, 256]); a policy with a width above 64 or with PHX_ACT_TANH is served by
+ * phx_sc_rollout_policy_mfma_kernel, f32 MFMA for the hidden-to-hidden layer: each v_mfma_f32_32x32x2_f32 is the k-ascending fmaf chain
+ * of the definition above, so the results are the definition's, bit for bit. */
 #define PHX_POLICY_MAX_WIDTH 64
+#define PHX_POLICY_WIDE_MAX  256
+#define PHX_POLICY_WIDE_STEP 32
 typedef struct phx_policy_mlp {
   int32_t n_hidden;            /* hidden layers: 1 or 2                                     */
-  int32_t width[2];            /* their units, 1 .. PHX_POLICY_MAX_WIDTH                    */
+  int32_t width[2];            /* their units, 1 .. 64 or 96, 128, .. PHX_POLICY_WIDE_MAX   */
   int32_t activation;          /* PHX_ACT_*                                                 */
   float   out_scale, out_bias; /* a = fmaf(out_scale, y, out_bias)                          */
   float   out_lo, out_hi;      /* action = clip(a, out_lo, out_hi)                          */

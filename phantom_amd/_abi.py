@@ -29,6 +29,7 @@ TAG_PYF, TAG_F32, TAG_F64 = 0, 1, 2      # PHX_TAG_*: numpy scalar kind of an ad
 ENV_PLAIN, ENV_FSM, ENV_STACKELBERG = 0, 1, 2
 # phx_spec.variant_* (ABI 6)
 VR_AUTO, VR_TIME_PARALLEL, VR_LEAN, VR_GENERAL, VR_LAUNCH_LOOP, VR_STORE_WAVES = 0, 1, 2, 3, 4, 5
+VR_POLICY_MFMA = 6
 VB_WHOLE_ENVS = -1
 VS_AUTO, VS_FUSED, VS_GENERIC, VS_WIDE, VS_GENERIC_DYNAMIC = 0, 1, 2, 3, 4
 SAMPLER_HOST, SAMPLER_UNIFORM = 0, 1
@@ -104,8 +105,9 @@ class PhxPolicyMLP(C.Structure):
                 ("w", C.c_void_p * 3), ("b", C.c_void_p * 3)]
 
 
-ACT_RELU, ACT_HARD_TANH = 0, 1
+ACT_RELU, ACT_HARD_TANH, ACT_TANH = 0, 1, 2
 POLICY_MAX_WIDTH = 64
+POLICY_WIDE_MAX, POLICY_WIDE_STEP = 256, 32
 
 
 class PhxStageRule(C.Structure):

@@ -23,6 +23,8 @@ hipError_t phx_launch_sc_rollout_fsm_rules(const DevSpec& sp, const phx_rollout_
 static const int SC_RULES_MAX_S = 256;      // (whole envs per 256-lane workgroup)
 const char* phx_sc_policy_unsupported(const DevSpec& sp, const phx_rollout_io& io);
 hipError_t phx_launch_sc_rollout_policy(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st);
+bool phx_sc_policy_wants_mfma(const DevSpec& sp, const phx_rollout_io& io);
+hipError_t phx_launch_sc_rollout_policy_mfma(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st);
 bool phx_sched_compile(const phx_spec* spec, int A, int n_lists, const int32_t* act_ptr, const int32_t* act_idx, const uint8_t* act_mask,
                        const uint8_t* obs_mask, const uint8_t* rew_mask, const int32_t* kind_rank, const int32_t* exo_rank, const int32_t* strat_rank,
                        const int32_t* reset_obs_idx, int n_reset_obs, std::vector<int32_t>* blob, std::vector<int32_t>* recs, int* L_out, int* qmax_out);
@@ -758,6 +760,8 @@ int phx_create(const phx_spec* spec, int device, void* state_blob, int64_t state
   d.n_lists = der.n_lists; d.initial_stage = spec->initial_stage; d.buyer_nnz = der.buyer_nnz; d.buyer_stride = der.kind_count[PHX_KIND_BUYER];
   d.seed = spec->seed; d.env_offset = spec->env_offset;
   d.variant_rollout = spec->variant_rollout; d.variant_block = spec->variant_block; d.variant_step = spec->variant_step;
+  d.policy_mfma = d.variant_rollout == PHX_VR_POLICY_MFMA;             // (a policy-kernel choice: every other path sees PHX_VR_AUTO)
+  if (d.policy_mfma) d.variant_rollout = PHX_VR_AUTO;
   memcpy(d.kind_count, der.kind_count, sizeof d.kind_count);
   const int A = der.A;
 #define UP(dst, ptr, n) do { rc = upload(e, ptr, (size_t)(n), &d.dst); if (rc != PHX_OK) { phx_destroy(e); return rc; } } while (0)
@@ -1398,11 +1402,12 @@ static int rollout_impl(phx_env* e, const phx_rollout_io* io, void* stream) {
   if (e->d.n_samplers > 0 && !e->d.device_sampling)
     return fail(PHX_EUNSUPPORTED, "phx_rollout auto-resets on the device: every sampler must be PHX_SAMPLER_UNIFORM");
   HIPCHK(use_device(e));
-  if (io->policy) {                   // ABI 10: the policy evaluated on the device, one lane per (env, shop) (phx_sc_policy.hip)
+  if (io->policy) {                   // ABI 10: the policy evaluated on the device (phx_sc_policy.hip; tanh / wide / PHX_VR_POLICY_MFMA: phx_sc_policy_mfma.hip)
     if (!e->use_fused) return fail(PHX_EUNSUPPORTED, "phx_rollout: `policy` needs a plain supply-chain env on its fused schedule");
     const char* why = phx_sc_policy_unsupported(e->d, *io);
     if (why) return fail(strstr(why, "phx_policy_mlp") ? PHX_EINVAL : PHX_EUNSUPPORTED, "phx_rollout: %s", why);
-    HIPCHK(phx_launch_sc_rollout_policy(e->d, *io, (hipStream_t)stream));
+    if (phx_sc_policy_wants_mfma(e->d, *io)) HIPCHK(phx_launch_sc_rollout_policy_mfma(e->d, *io, (hipStream_t)stream));      // phx_sc_policy_mfma.hip
+    else HIPCHK(phx_launch_sc_rollout_policy(e->d, *io, (hipStream_t)stream));
     return PHX_OK;
   }
   if (e->use_ads && e->n_inject == 0) {

@@ -151,6 +151,7 @@ struct DevSpec {
   const uint8_t* sc_shop_flags;  // [n_lists][nS] 1 shop acts, 2 a customer acts, 4 every customer acts, 8 observes, 16 rewarded
   int32_t max_cust;              // max customers of one shop
   int32_t variant_rollout, variant_block, variant_step;   // phx_spec.variant_* (0 = the library's choice)
+  int32_t policy_mfma;          // phx_spec.variant_rollout was PHX_VR_POLICY_MFMA (then variant_rollout = PHX_VR_AUTO for every other path)
   ScFastPlan sc_fast;            // fast rollout kernel: plan (ok == 0: not applicable)
   int32_t sc_wide_K, sc_wide_norm;   // phx_sc_step_wide_kernel: the shops' common customer count (0: the kernel does not apply) and normaliser
   ScSwPlan sc_sw;                // store-wave rollout kernel (round 4): plan (ok == 0: not applicable)

@@ -19,27 +19,10 @@
 //     workgroup only.
 // Bound: at B = 4096 the launch is 0.6 waves per SIMD and every step a dependent chain (~100 fmas + the output accumulation)
 // -- latency, not HBM: 22 S bytes per env-step leave as plain per-lane stores.
-#include "phx_dev.h"
+#include "phx_sc_policy.h"
 
 #include <cstring>
 
-struct PolArgs {
-  int32_t B, S, epb, T, num_steps, n_exo;
-  uint64_t seed; int64_t env_offset;
-  int32_t *stock, *sales, *missed, *delivered, *env_step, *env_tick;
-  const int32_t* shop_norm; const int32_t* shop_cust_ptr; const int32_t* shop_cust_exo;
-  phx_rollout_io io;
-  phx_policy_mlp pol;
-};
-
-// act(c) as ONE v_med3_f32: ReLU = the median of (c, 0, +inf), hard-tanh = the median of (c, -1, 1).  Finite c: the values of the header's
-// definition (c > 0 ? c : +0 / the two-sided clip); a -0 that med3 may let through where the definition says +0 changes no sum's value and the
-// definition's closing "+ 0.0f" removes it from the action.
-template <int ACT>
-__device__ __forceinline__ float pol_act(float c) {
-  if (ACT == PHX_ACT_HARD_TANH) return __builtin_amdgcn_fmed3f(c, -1.0f, 1.0f);
-  return __builtin_amdgcn_fmed3f(c, 0.0f, __builtin_inff());
-}
 typedef float pol_f2 __attribute__((ext_vector_type(2)));
 
 // LDS image of the network (floats), staged once per workgroup -- every lane reads the same addresses (broadcast reads, 16 bytes =
@@ -93,34 +76,11 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
   const int el = on ? tid / S : 0, s = on ? tid - el * S : 0;
   const int b = b0 + el;
   const int64_t pair = (int64_t)b * S + s, total = (int64_t)a.B * S;
-  int stock = a.stock[pair], sales = a.sales[pair], missed = a.missed[pair], delivered = a.delivered[pair];
-  int step = a.env_step[b]; uint32_t tick = (uint32_t)a.env_tick[b];
-  // (a "use" of every loaded word HERE: `delivered` is overwritten by the first step without ever being read, and the s_waitcnt vmcnt(0) that
-  //  protects its register from the load still in flight would otherwise sit inside the step loop -- where it waits for the row's stores)
-  asm volatile("" :: "v"(stock), "v"(sales), "v"(missed), "v"(delivered), "v"(step), "v"(tick));
-  const int norm_i = a.shop_norm[s];
-  const float norm_f = (float)norm_i;
-  const int c0 = a.shop_cust_ptr[s], K = a.shop_cust_ptr[s + 1] - c0;
-  const int64_t genv = a.env_offset + b;
-  const float out_scale = a.pol.out_scale, out_bias = a.pol.out_bias, out_lo = a.pol.out_lo, out_hi = a.pol.out_hi;
-  // the divisors never change: their reciprocals once (IEEE divisions), a quotient = a multiply and Markstein's correction (phx_dev.h: div_by_recip)
-  const float r_stock = 1.0f / (float)PHX_SHOP_MAX_STOCK, r_norm = 1.0f / norm_f;
-  const bool norm_small = norm_i >= 1 && norm_i <= DIV_RECIP_N;
-  auto encode = [&](int st, int sl, int ms, float* o) {                // ShopAgent.encode_observation, supply_chain.py:124-134
-    if (__builtin_expect(norm_small && (unsigned)(st | sl | ms) < (unsigned)DIV_RECIP_X, 1)) {
-      o[0] = div_by_recip((float)st, (float)PHX_SHOP_MAX_STOCK, r_stock);
-      o[1] = div_by_recip((float)sl, norm_f, r_norm);
-      o[2] = div_by_recip((float)ms, norm_f, r_norm);
-    } else if ((((unsigned)st + (1u << 24)) | ((unsigned)sl + (1u << 24)) | ((unsigned)ms + (1u << 24)) | ((unsigned)norm_i + (1u << 24))) < (2u << 24))
-      shop_obs_f32(st, sl, ms, norm_f, o);
-    else shop_obs(st, sl, ms, norm_i, o);
-  };
+  PolShop sh;                                                          // the row's state and constants (phx_sc_policy.h)
+  sh.load(a, pair, b, s);
   float x[3];
-  encode(stock, sales, missed, x);                                     // what the agent observes now: the policy's first input
-  const bool small_k = __all(K <= 6) != 0;
-  const uint32_t pK = K <= 0 ? 1u : K == 1 ? 5u : K == 2 ? 25u : K == 3 ? 125u : K == 4 ? 625u : K == 5 ? 3125u : 15625u;
-  const float inv_pK = K <= 0 ? 1.0f : K == 1 ? 0.2f : K == 2 ? 0.04f : K == 3 ? 0.008f : K == 4 ? 0.0016f : K == 5 ? 0.00032f : 0.000064f;
-  RngQuadCache quad; quad.q = 0xffffffffu; quad.w[0] = quad.w[1] = quad.w[2] = quad.w[3] = 0u;
+  sh.encode(sh.stock, sh.sales, sh.missed, x);                         // what the agent observes now: the policy's first input
+  sh.orders_init();
   float* const hcol = s_h + tid;
   const float4* const img0 = (const float4*)s_img;                     // layer 0, one float4 per unit
   const float* const o1 = s_img + 4 * W0p;
@@ -229,34 +189,12 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
         y = __fmaf_rn(wb.x, pol_act<ACT>(c[4]), y); y = __fmaf_rn(wb.y, pol_act<ACT>(c[5]), y); y = __fmaf_rn(wb.z, pol_act<ACT>(c[6]), y); y = __fmaf_rn(wb.w, pol_act<ACT>(c[7]), y);
       }
     }
-    const float av = __fmaf_rn(out_scale, y, out_bias);
-    const float action = (av < out_lo ? out_lo : (av > out_hi ? out_hi : av)) + 0.0f;      // (+ 0.0f: an exact zero leaves as +0)
+    const float action = pol_action(a.pol, y);
 
     // ---- PhantomEnv.step for the pair (env.py:239-303 with the supply chain's closed form) -------------------------------------------
-    int D = 0;                                                         // the shop's customers' order sizes summed, supply_chain.py:61-67
-    if (EXO) {
-      const uint8_t* row = a.io.exo + ((int64_t)t * a.B + b) * a.n_exo;
-      for (int k = 0; k < K; ++k) D += (int)row[a.shop_cust_exo[c0 + k]];
-    } else {
-      rng_quad_block(quad, a.seed, genv, tick, s);
-      if (small_k) {                                                   // (uniform) every shop of the wave has at most six customers: one word, its first K base-5 digits
-        uint32_t y, jr;
-        if (__builtin_expect(!rng_split(rng_pick(quad.w, tick), y, jr), 0)) y = rng_group_y(a.seed, genv, tick, s, 0, 1);      // probability 3.3e-6
-        y -= __umul24((uint32_t)((float)y * inv_pK), pK);              // y mod 5^K (exact through f32: tests/test_host_logic.py)
-        D = rng_digit_sum6(y);
-      } else D = rng_orders_from_block(quad.w, a.seed, genv, tick, s, K, nullptr, nullptr);
-    }
-    const int req = dev_round_half_even(action), room = PHX_SHOP_MAX_STOCK - stock;      // decode_action :136-142 (the stock BEFORE the step)
-    const int deliv = req < room ? req : room;
-    const int sell = stock < D ? stock : D;                            // handle_order_request, order after order: sells what is left (:105-122)
-    sales = sell; missed = D - sell;
-    stock = stock - sell + deliv;                                      // handle_stock_response (:98-103): deliv <= 100 - stock
-    delivered = deliv;
-    const int t_ep = step + 1;
-    const bool trunc = t_ep == a.num_steps;                            // truncations["__all__"], env.py:312-318
-    float ob[3];
-    encode(stock, sales, missed, ob);
-    const float rw = (float)shop_reward(sales, stock);                 // compute_reward :147, rounded once to f32
+    const int D = sh.orders<EXO>(a, t, b, s);
+    float ob[3], rw;
+    const bool trunc = sh.advance(a, action, D, ob, rw);
     if (on) {                                                          // the trajectory row, rollout.py:361-389 (running pointers: one 64-bit add per plane and step)
       p_obs[0] = ob[0]; p_obs[1] = ob[1]; p_obs[2] = ob[2];
       *p_act = action;
@@ -265,17 +203,9 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
       *p_tru = trunc ? 1 : 0;
       p_obs += total * 3; p_act += total; p_rew += total; p_tru += total;
     }
-    ++tick;
-    if (trunc) {                                                       // the caller's env.reset(): ShopAgent.reset zeroes the stock (:149-150); sales stay (App. B)
-      stock = 0; step = 0;
-      encode(0, sales, missed, x);
-    } else { step = t_ep; x[0] = ob[0]; x[1] = ob[1]; x[2] = ob[2]; }
+    sh.next(trunc, ob, x);                                             // the caller's env.reset() at an episode's end; the next input
   }
-  if (on) {
-    a.stock[pair] = stock; a.sales[pair] = sales; a.missed[pair] = missed; a.delivered[pair] = delivered;
-    if (a.io.last_obs) { float* lo = a.io.last_obs + pair * 3; lo[0] = x[0]; lo[1] = x[1]; lo[2] = x[2]; }
-    if (s == 0) { a.env_step[b] = step; a.env_tick[b] = (int32_t)tick; }
-  }
+  if (on) sh.store(a, pair, b, s, x);
 }
 
 // host: serves the call?  (plain supply chain on the fused schedule, ShopAgent observations, whole envs in a 256-lane workgroup)
@@ -283,11 +213,25 @@ const char* phx_sc_policy_unsupported(const DevSpec& sp, const phx_rollout_io& i
   const phx_policy_mlp& p = *io.policy;
   if (sp.env_type != PHX_ENV_PLAIN || sp.any_typed || sp.D != 3 || sp.S < 1 || sp.S > 128 || sp.S != sp.kind_count[PHX_KIND_SHOP]) return "the policy kernel serves plain supply-chain envs (ShopAgent observations, at most 128 shops)";
   if (p.n_hidden < 1 || p.n_hidden > 2) return "phx_policy_mlp: 1 or 2 hidden layers";
-  for (int l = 0; l < p.n_hidden; ++l) if (p.width[l] < 1 || p.width[l] > PHX_POLICY_MAX_WIDTH) return "phx_policy_mlp: hidden widths 1 .. 64";
-  if (p.activation != PHX_ACT_RELU && p.activation != PHX_ACT_HARD_TANH) return "phx_policy_mlp: unknown activation";
+  for (int l = 0; l < p.n_hidden; ++l) {
+    const int w = p.width[l];
+    if (w < 1 || (w > PHX_POLICY_MAX_WIDTH && (w > PHX_POLICY_WIDE_MAX || w % PHX_POLICY_WIDE_STEP != 0)))
+      return "phx_policy_mlp: hidden widths 1 .. 64, or multiples of 32 from 96 to 256";
+  }
+  if (p.activation != PHX_ACT_RELU && p.activation != PHX_ACT_HARD_TANH && p.activation != PHX_ACT_TANH)
+    return "phx_policy_mlp: unknown activation (PHX_ACT_RELU, PHX_ACT_HARD_TANH or PHX_ACT_TANH)";
   for (int l = 0; l <= p.n_hidden; ++l) if (!p.w[l] || !p.b[l] || ((uintptr_t)p.w[l] & 3u) || ((uintptr_t)p.b[l] & 3u)) return "phx_policy_mlp: a weight / bias pointer is NULL or misaligned";
   if (!(p.out_lo >= 0.0f) || !(p.out_hi >= p.out_lo)) return "phx_policy_mlp: 0 <= out_lo <= out_hi (ShopAgent's action space)";
   return nullptr;
+}
+
+// host: which kernel serves a policy phx_sc_policy_unsupported accepted -- tanh and wide layers only phx_sc_policy_mfma.hip's; ReLU /
+// hard-tanh of widths <= 64 this file's, unless the spec asked for PHX_VR_POLICY_MFMA
+bool phx_sc_policy_wants_mfma(const DevSpec& sp, const phx_rollout_io& io) {
+  const phx_policy_mlp& p = *io.policy;
+  if (sp.policy_mfma || p.activation == PHX_ACT_TANH) return true;
+  for (int l = 0; l < p.n_hidden; ++l) if (p.width[l] > PHX_POLICY_MAX_WIDTH) return true;
+  return false;
 }
 
 hipError_t phx_launch_sc_rollout_policy(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st) {

@@ -1,8 +1,8 @@
 """A policy evaluated on the device inside the fused rollout (``phx_rollout_io.policy``, ABI 10).
 
 The reference's collection loop calls a policy for every agent and step (utils/rllib/rollout.py:300-363).  ``MLPPolicy`` is the
-small network the library can evaluate itself, one lane per (env, shop): ``DeviceEnv.rollout(T, policy=pol)`` is ONE launch for T
-on-policy steps.  Its arithmetic is defined in include/phantom_amd.h (f32, fused multiply-adds term by term in ascending order);
+network the library can evaluate itself (up to RLlib's default model, two hidden layers of 256 tanh units):
+``DeviceEnv.rollout(T, policy=pol)`` is ONE launch for T on-policy steps.  Its arithmetic is defined in include/phantom_amd.h (f32, fused multiply-adds term by term in ascending order);
 ``__call__`` evaluates the same network with torch ops (the same function up to the order of the additions)."""
 import ctypes as C
 from typing import Optional, Sequence
@@ -11,12 +11,18 @@ import numpy as np
 
 from . import _abi
 
-ACTIVATIONS = {"relu": _abi.ACT_RELU, "hard_tanh": _abi.ACT_HARD_TANH}
+ACTIVATIONS = {"relu": _abi.ACT_RELU, "hard_tanh": _abi.ACT_HARD_TANH, "tanh": _abi.ACT_TANH}
+
+
+def width_ok(w: int) -> bool:
+    """a hidden width the device serves: 1 .. 64, or a multiple of 32 up to 256"""
+    return 1 <= w <= _abi.POLICY_MAX_WIDTH or (1 <= w <= _abi.POLICY_WIDE_MAX and w % _abi.POLICY_WIDE_STEP == 0)
 
 
 class MLPPolicy:
     """``weights`` / ``biases``: torch.nn.Linear's own layouts -- [H0, D], ([H1, H0],) [1, H_last] and [H0], ([H1],) [1]; one or two
-    hidden layers of at most 64 units; ``activation`` "relu" or "hard_tanh" (clip to [-1, 1]).  The scalar output y becomes the action
+    hidden layers of 1 .. 64 units or a multiple of 32 up to 256; ``activation`` "relu", "hard_tanh" (clip to [-1, 1]) or "tanh" (the
+    header's PHX_ACT_TANH, within 4e-7 of tanh).  The scalar output y becomes the action
     ``clip(out_scale * y + out_bias, out_lo, out_hi)`` (ShopAgent's action space is Box(0, 100): out_lo >= 0)."""
 
     def __init__(self, weights: Sequence, biases: Sequence, activation: str = "relu", out_scale: float = 1.0, out_bias: float = 0.0,
@@ -32,8 +38,9 @@ class MLPPolicy:
             w, b = self.weights[l], self.biases[l]
             if w.ndim != 2 or b.shape != (w.shape[0],) or (l > 0 and w.shape[1] != self.weights[l - 1].shape[0]):
                 raise ValueError(f"MLPPolicy: layer {l} has weight {w.shape} and bias {b.shape}")
-            if l < n - 1 and not 1 <= w.shape[0] <= _abi.POLICY_MAX_WIDTH:
-                raise ValueError(f"MLPPolicy: hidden widths 1 .. {_abi.POLICY_MAX_WIDTH}")
+            if l < n - 1 and not width_ok(w.shape[0]):
+                raise ValueError(f"MLPPolicy: hidden width {w.shape[0]}: 1 .. {_abi.POLICY_MAX_WIDTH}, or a multiple of "
+                                 f"{_abi.POLICY_WIDE_STEP} up to {_abi.POLICY_WIDE_MAX}")
             if not (np.isfinite(w).all() and np.isfinite(b).all()):
                 raise ValueError("MLPPolicy: weights must be finite")
         if self.weights[-1].shape[0] != 1:
@@ -50,12 +57,37 @@ class MLPPolicy:
 
     @classmethod
     def from_torch(cls, module, **kw) -> "MLPPolicy":
-        """from a torch.nn.Sequential of Linear layers with ReLU / Hardtanh between them"""
+        """from a torch.nn.Sequential: Linear, activation, Linear[, activation, Linear] in that order -- ReLU, Hardtanh(-1, 1) or Tanh,
+        the same one between every pair of Linears.  Any other layer, mixed activations, two Linears in a row or a Hardtanh with other
+        bounds raise ValueError.  RLlib's action head for a Box action space outputs (mean, log_std): pass a module whose last Linear is
+        the MEAN row only (``weight[:1]``, ``bias[:1]``) -- the device policy is deterministic (explore = False)."""
         import torch
-        lin = [m for m in module.modules() if isinstance(m, torch.nn.Linear)]
-        acts = [m for m in module.modules() if isinstance(m, (torch.nn.ReLU, torch.nn.Hardtanh))]
-        act = "hard_tanh" if acts and isinstance(acts[0], torch.nn.Hardtanh) else "relu"
-        return cls([m.weight.detach() for m in lin], [m.bias.detach() for m in lin], activation=act, **kw)
+        kinds = {torch.nn.ReLU: "relu", torch.nn.Tanh: "tanh", torch.nn.Hardtanh: "hard_tanh"}
+        layers = list(module.children()) if len(list(module.children())) else [module]
+        lin, acts = [], []
+        for i, m in enumerate(layers):
+            want_linear = i % 2 == 0
+            if want_linear:
+                if type(m) is not torch.nn.Linear:
+                    raise ValueError(f"MLPPolicy.from_torch: layer {i} is {type(m).__name__}, a Linear is expected there")
+                if m.bias is None:
+                    raise ValueError(f"MLPPolicy.from_torch: layer {i} has no bias")
+                lin.append(m)
+                continue
+            kind = kinds.get(type(m))
+            if kind is None:
+                raise ValueError(f"MLPPolicy.from_torch: layer {i} is {type(m).__name__}: ReLU, Hardtanh(-1, 1) or Tanh expected "
+                                 "between Linears")
+            if kind == "hard_tanh" and (float(m.min_val) != -1.0 or float(m.max_val) != 1.0):
+                raise ValueError(f"MLPPolicy.from_torch: layer {i} is Hardtanh({m.min_val}, {m.max_val}); only Hardtanh(-1, 1)")
+            acts.append(kind)
+        if not lin or len(layers) % 2 == 0:
+            raise ValueError("MLPPolicy.from_torch: the module must end with a Linear")
+        if len(set(acts)) > 1:
+            raise ValueError(f"MLPPolicy.from_torch: mixed activations {acts}; one kind between every pair of Linears")
+        if not acts:
+            raise ValueError("MLPPolicy.from_torch: at least one hidden layer (Linear, activation, Linear)")
+        return cls([m.weight.detach() for m in lin], [m.bias.detach() for m in lin], activation=acts[0], **kw)
 
     def update(self, weights: Sequence, biases: Sequence) -> None:
         """new parameter values of the same shapes (a learner's update): the device copies are refreshed in place, cached argument
@@ -97,13 +129,19 @@ class MLPPolicy:
         return self._c_struct([w.ctypes.data for w in self.weights], [b.ctypes.data for b in self.biases])
 
     def __call__(self, obs):
-        """the network on a torch tensor [..., D] with torch ops (same function; the additions are not in the device's order)"""
+        """the network on a torch tensor [..., D] with torch ops (same function up to the order of the additions -- and, for tanh,
+        torch.tanh against the header's approximation, within 4e-7)"""
         import torch
         ws, bs, _ = self.on(obs.device)
         h = obs
         for l in range(len(ws) - 1):
             h = torch.nn.functional.linear(h, ws[l], bs[l])
-            h = torch.clamp(h, -1.0, 1.0) if self.activation == "hard_tanh" else torch.relu(h)
+            if self.activation == "hard_tanh":
+                h = torch.clamp(h, -1.0, 1.0)
+            elif self.activation == "tanh":
+                h = torch.tanh(h)
+            else:
+                h = torch.relu(h)
         y = torch.nn.functional.linear(h, ws[-1], bs[-1]).squeeze(-1)
         return torch.clamp(y * self.out_scale + self.out_bias, self.out_lo, self.out_hi)
 
