@@ -116,6 +116,12 @@ int phx_rollout(phx_env* e, const phx_rollout_io* io, void* stream) {
   (void)stream;
   if (!e || !io || io->T <= 0) return PHX_EINVAL;
   if ((io->hints & ~(PHX_RH_ACTIONS_IN_DOMAIN | PHX_RH_EXO_IN_DOMAIN)) != 0 || io->reserved_ptr) return PHX_EINVAL;   /* (the hints change nothing here: this path never relies on them, so it reports no PHX_ERR_HINT either) */
+  if (io->policy) {                                      /* the HIP library's order (phx_api.hip, phx_sc_policy_unsupported): what `policy` excludes, the env, then the network */
+    if (io->actions || io->n_frag >= 2 || io->frags || io->msg_log || io->msg_count) return PHX_EINVAL;
+    const int S = phxo_n_strategic(e->o);
+    if (e->env_type != PHX_ENV_PLAIN || phxo_obs_dim(e->o) != 3 || S < 1 || S > 128) return PHX_EUNSUPPORTED;
+    return phxo_rollout(e->o, io);                       /* PHX_EINVAL for a network the device refuses */
+  }
   if (io->n_frag >= 2 || io->frags) {                    /* ABI 9, a fragment list: the same steps, the rows handed out fragment by fragment */
     if (io->n_frag < 2 || io->n_frag > PHX_MAX_FRAGMENTS || !io->frags || io->T % io->n_frag) return PHX_EINVAL;
     if (io->obs || io->action_out || io->reward || io->terminated || io->truncated || io->obs_valid || io->reward_valid) return PHX_EINVAL;
@@ -140,8 +146,7 @@ int phx_rollout(phx_env* e, const phx_rollout_io* io, void* stream) {
     }
     return PHX_OK;
   }
-  phxo_rollout(e->o, io);
-  return PHX_OK;
+  return phxo_rollout(e->o, io);
 }
 
 /* copying state access by field name: the restatement knows a field as i32, f64 or u8 */

@@ -1272,16 +1272,55 @@ static float policy_action(const phxo_env* E, const oenv* e, int b, int s) {
 }
 
 /* phx_policy_mlp (include/phantom_amd.h): the device-evaluated policy of a rollout, restated term by term -- fmaf is C99's correctly
- * rounded fused multiply-add, so the value does not depend on the machine; the host copies of the weights are made by the test harness
- * (the struct's pointers are HOST pointers here).                                                                                      */
+ * rounded fused multiply-add and * and / are plain f32 operations (the Makefile builds with -ffp-contract=off), so the value does not
+ * depend on the machine; the host copies of the weights are made by the test harness (the struct's pointers are HOST pointers here).
+ * phxo_policy_check refuses what the device refuses (phx_sc_policy_unsupported's policy rules) before a policy reaches the buffers below. */
+int phxo_policy_check(const phx_policy_mlp* p) {
+  if (!p || p->n_hidden < 1 || p->n_hidden > 2) return PHX_EINVAL;
+  for (int l = 0; l < p->n_hidden; ++l) {
+    const int w = p->width[l];
+    if (w < 1 || (w > PHX_POLICY_MAX_WIDTH && (w > PHX_POLICY_WIDE_MAX || w % PHX_POLICY_WIDE_STEP != 0))) return PHX_EINVAL;
+  }
+  if (p->activation != PHX_ACT_RELU && p->activation != PHX_ACT_HARD_TANH && p->activation != PHX_ACT_TANH) return PHX_EINVAL;
+  for (int l = 0; l <= p->n_hidden; ++l)
+    if (!p->w[l] || !p->b[l] || ((uintptr_t)p->w[l] & 3u) || ((uintptr_t)p->b[l] & 3u)) return PHX_EINVAL;
+  if (!(p->out_lo >= 0.0f) || !(p->out_hi >= p->out_lo)) return PHX_EINVAL;
+  return PHX_OK;
+}
+
+/* PHX_ACT_TANH as the header defines it, step for step (the header's PHX_TANH_* coefficients) */
+static float policy_tanh(float c) {
+  const float a = fabsf(c);
+  float t;
+  if (!(a < PHX_TANH_SAT)) t = 1.0f;
+  else if (a < PHX_TANH_SMALL) t = a;
+  else {
+    const float s = a * a;
+    float p = PHX_TANH_A13;
+    p = fmaf(p, s, PHX_TANH_A11); p = fmaf(p, s, PHX_TANH_A9); p = fmaf(p, s, PHX_TANH_A7);
+    p = fmaf(p, s, PHX_TANH_A5); p = fmaf(p, s, PHX_TANH_A3); p = fmaf(p, s, PHX_TANH_A1);
+    float q = PHX_TANH_B6;
+    q = fmaf(q, s, PHX_TANH_B4); q = fmaf(q, s, PHX_TANH_B2); q = fmaf(q, s, PHX_TANH_B0);
+    t = (a * p) / q;
+    t = t > 1.0f ? 1.0f : t;
+  }
+  return copysignf(t, c);
+}
+
+static float policy_act(int act, float c) {
+  if (act == PHX_ACT_TANH) return policy_tanh(c);
+  if (act == PHX_ACT_HARD_TANH) return c < -1.0f ? -1.0f : (c > 1.0f ? 1.0f : c);
+  return c > 0.0f ? c : 0.0f;
+}
+
 static float policy_mlp_action(const phx_policy_mlp* p, const float* x, int D) {
-  float h[2][PHX_POLICY_MAX_WIDTH];
+  float h[2][PHX_POLICY_WIDE_MAX];                                    /* (phxo_policy_check: widths <= PHX_POLICY_WIDE_MAX) */
   const float* in = x; int n_in = D;
   for (int l = 0; l < p->n_hidden; ++l) {
     for (int i = 0; i < p->width[l]; ++i) {
       float c = p->b[l][i];
       for (int k = 0; k < n_in; ++k) c = fmaf(p->w[l][(size_t)i * n_in + k], in[k], c);
-      h[l][i] = p->activation == PHX_ACT_HARD_TANH ? (c < -1.0f ? -1.0f : (c > 1.0f ? 1.0f : c)) : (c > 0.0f ? c : 0.0f);
+      h[l][i] = policy_act(p->activation, c);
     }
     in = h[l]; n_in = p->width[l];
   }
@@ -1347,9 +1386,14 @@ static void rollout_one(phxo_env* E, const phx_rollout_io* io, int b) {
   if (io->err) io->err[b] = e->err;
 }
 
-void phxo_rollout(phxo_env* E, const phx_rollout_io* io) {
+int phxo_rollout(phxo_env* E, const phx_rollout_io* io) {
+  if (io->policy) {
+    const int rc = phxo_policy_check(io->policy);
+    if (rc != PHX_OK) return rc;
+  }
 #pragma omp parallel for num_threads(g_threads) schedule(static)
   for (int b = 0; b < E->B; ++b) rollout_one(E, io, b);
+  return PHX_OK;
 }
 
 /* ---- state read-back -------------------------------------------------------------------------- */

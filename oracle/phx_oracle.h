@@ -42,7 +42,10 @@ void phxo_step_begin(phxo_env* e, const phx_step_io* io);   /* acting phase + re
 void phxo_step_end(phxo_env* e, const phx_step_io* io);     /* io->next_stage -> transition, observations, rewards, done flags (fsm.py:304-380) */
 void phxo_inject(phxo_env* e, const phx_msg_rec* msgs, int n);
 void phxo_resolve(phxo_env* e, int32_t* err, phx_msg_rec* msg_log, int32_t* msg_count);
-void phxo_rollout(phxo_env* e, const phx_rollout_io* io);
+/* PHX_OK, or PHX_EINVAL for a policy the device refuses (io->policy; nothing is written then) */
+int  phxo_rollout(phxo_env* e, const phx_rollout_io* io);
+/* phx_policy_mlp's rules as the device applies them (hidden layers, widths, activation, pointers, out_lo / out_hi): PHX_OK or PHX_EINVAL */
+int  phxo_policy_check(const phx_policy_mlp* p);
 
 /* state read-back by field name, shape [B][count-of-that-kind] (or [B] for env fields);
  * returns number of elements written, -1 for an unknown field                           */

@@ -56,7 +56,10 @@ def lib():
             getattr(L, _n).argtypes = [vp, C.POINTER(_abi.PhxStepIO)]
         L.phxo_inject.argtypes = [vp, C.POINTER(_abi.PhxMsgRec), C.c_int]
         L.phxo_resolve.argtypes = [vp, vp, vp, vp]
+        L.phxo_rollout.restype = C.c_int
         L.phxo_rollout.argtypes = [vp, C.POINTER(_abi.PhxRolloutIO)]
+        L.phxo_policy_check.restype = C.c_int
+        L.phxo_policy_check.argtypes = [C.POINTER(_abi.PhxPolicyMLP)]
         for n in ("phxo_get_i32", "phxo_get_f64", "phxo_set_i32"):
             getattr(L, n).restype = C.c_int64
             getattr(L, n).argtypes = [vp, C.c_char_p, vp]
@@ -188,14 +191,18 @@ class OracleEnv:
         io.terminated, io.truncated = _p(out["terminated"]), _p(out["truncated"])
         io.obs_valid, io.reward_valid = _p(out["obs_valid"]), _p(out["reward_valid"])
         io.last_obs, io.err = _p(out["last_obs"]), _p(self.err)
-        if policy is not None:                                  # phantom_amd.policy.MLPPolicy: the restatement reads the host copies of the weights
-            self._pol = policy.host_struct()
+        if policy is not None:                                  # phantom_amd.policy.MLPPolicy (its host copies of the weights), or a phx_policy_mlp of host pointers
+            self._pol = policy.host_struct() if hasattr(policy, "host_struct") else policy
+            if self.L.phxo_policy_check(C.byref(self._pol)) != 0:
+                raise ValueError("OracleEnv.rollout: a policy the device refuses (phx_sc_policy_unsupported's rules)")
             io.policy = C.addressof(self._pol)
         if record_messages:
             out["msg_log"] = np.zeros((T, B, self.spec.trace_cap), LOG_DTYPE)
             out["msg_count"] = np.zeros((T, B), np.int32)
             io.msg_log, io.msg_count = _p(out["msg_log"]), _p(out["msg_count"])
-        self.L.phxo_rollout(self.h, C.byref(io))
+        rc = self.L.phxo_rollout(self.h, C.byref(io))
+        if rc != 0:
+            raise ValueError(f"phxo_rollout: {rc}")
         return out
 
     def get_i32(self, field):

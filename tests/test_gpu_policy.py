@@ -114,3 +114,26 @@ def test_policy_update_and_argument_errors():
     mk = DeviceRunner(market_env(4, 8, 2, 6, 4).spec); mk.reset()
     with pytest.raises((DeviceError, ValueError)):
         mk.dev.rollout(4, policy=_policy((4,), "relu", 1))
+
+
+@pytest.mark.parametrize("widths,act", [((64, 64), "relu"), ((8, 3), "hard_tanh"), ((17, 33), "relu"), ((24, 16), "hard_tanh")])
+@pytest.mark.parametrize("S", [65, 100, 128])
+def test_two_hidden_layers_with_one_env_per_workgroup(S, widths, act):
+    """two hidden layers run 128-lane workgroups: for S > 64 one env each (S = 128: every lane a row) -- the oracle's rows, last_obs and
+    state, two fragments with episode ends inside, then replayed order sizes"""
+    B, ns = 4, 6
+    env = supply_chain_env(S, [1 + s % 5 for s in range(S)], ns, B, seed=5 + S, env_offset=2)
+    o, d = OracleEnv(env.spec, threads=4), DeviceRunner(env.spec)
+    o.reset(); d.reset()
+    pol = _policy(widths, act, seed=S + widths[0])
+    for rep, T in enumerate((2 * ns + 3, 9)):
+        ro, rd = o.rollout(T, policy=pol), d.rollout(T, policy=pol)
+        assert d.dev.last_kernel() == KERNEL, d.dev.last_kernel()
+        _cmp(rd, ro, f"rep {rep}")
+        for f in STATE:
+            np.testing.assert_array_equal(d.get_i32(f), o.get_i32(f), err_msg=f"{f} rep {rep}")
+        assert rep or rd["truncated"].any()
+    exo = np.random.default_rng(3).integers(0, 5, (8, B, d.n_exo)).astype(np.uint8)
+    _cmp(d.rollout(8, None, exo, policy=pol), o.rollout(8, None, exo, policy=pol), "replayed order sizes")
+    assert d.dev.last_kernel() == KERNEL
+    assert (d.err == 0).all()
