@@ -663,21 +663,6 @@ static int upload(phx_env* e, const T* host, size_t n, const T** out) {
 }
 
 static thread_local char g_kernels[384] = "";
-#ifdef PHX_TIMING
-// development builds: phase timers of the generic engine (10 ns ticks of thread 0, first 64 workgroups), dumped every PHX_TIMING_DUMP env-steps
-static unsigned long long* phx_gen_timing(int steps) {
-  static unsigned long long* tb = nullptr; static long done = 0, next = 0;
-  if (!tb) { (void)hipMalloc((void**)&tb, 16 * 8); (void)hipMemset(tb, 0, 16 * 8); next = getenv("PHX_TIMING_DUMP") ? atol(getenv("PHX_TIMING_DUMP")) : 0; }
-  if (next > 0 && done >= next) {
-    (void)hipDeviceSynchronize(); unsigned long long h[16]; (void)hipMemcpy(h, tb, sizeof h, hipMemcpyDeviceToHost); (void)hipMemset(tb, 0, 16 * 8);
-    const double n = (double)done * 64; double tot = 0; fprintf(stderr, "PHX_GTIMING ns/step:");
-    for (int q = 0; q < 16; ++q) { fprintf(stderr, " %d:%.0f", q, h[q] * 10.0 / n); tot += h[q] * 10.0 / n; }
-    fprintf(stderr, "  total %.0f\n", tot); done = 0;
-  }
-  done += steps;
-  return tb;
-}
-#endif
 static void note_reset() { g_kernels[0] = 0; }
 void phx_note_kernel(const char* name) {
   const size_t n = strlen(g_kernels), m = strlen(name);
@@ -687,40 +672,16 @@ void phx_note_kernel(const char* name) {
 
 extern "C" {
 
-// the development knobs: every PHX_* environment toggle of the library, read here and nowhere else (first use: phx_create)
-extern "C++" const DevKnobs& phx_knobs() {
-  static const DevKnobs knobs = [] {
-    DevKnobs k;
+// the process-wide switches: the only environment variables the library reads, here and nowhere else (first use: phx_create)
+extern "C++" const PhxSwitches& phx_switches() {
+  static const PhxSwitches sw = [] {
     auto rd = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-    k.fsm_fast = rd("PHX_FSM_FAST", -1);             // -1: unset; 0 off; 2 forces it at any batch size
-    k.fsm_lean = rd("PHX_FSM_LEAN", 1);
-    k.fsm_wide = rd("PHX_FSM_WIDE", 1);
-    k.fsm_batch = rd("PHX_FSM_BATCH", 1);
-    k.generic_nt = rd("PHX_GENERIC_NT", 0);
-    k.generic_remap = rd("PHX_GENERIC_REMAP", 1);
-    k.generic_tablds = rd("PHX_GENERIC_TABLDS", 1);
-    k.generic_sched = rd("PHX_GENERIC_SCHED", 1);
+    PhxSwitches k;
     k.autotune = rd("PHX_AUTOTUNE", 1);
-    k.rollout_epb = rd("PHX_ROLLOUT_EPB", 0);
-    k.rollout_fast = rd("PHX_ROLLOUT_FAST", -1);     // -1: unset; 0 switches the kernel off
-    k.rollout_first = rd("PHX_ROLLOUT_FIRST", 0);
-    k.rollout_g = rd("PHX_ROLLOUT_G", 0);
-    k.rollout_ldskb = rd("PHX_ROLLOUT_LDSKB", 0);
-    k.rollout_nt = rd("PHX_ROLLOUT_NT", 0);
-    k.rollout_remap = rd("PHX_ROLLOUT_REMAP", -1);
-    k.rollout_sparse_flags = rd("PHX_ROLLOUT_SPARSE_FLAGS", 1);
-    k.step_nt = rd("PHX_STEP_NT", 0);
-    k.stk_rollout_nt = rd("PHX_STK_ROLLOUT_NT", 0);
-    k.stk_step_fast = rd("PHX_STK_STEP_FAST", 1);
-    k.stk_step_nt = rd("PHX_STK_STEP_NT", 0);
-    k.sw_generic = rd("PHX_SW_GENERIC", 0);
-    k.sw_persist = rd("PHX_SW_PERSIST", 1);
-    k.sw_store_waves = rd("PHX_SW_STORE_WAVES", 0);
-    k.sw_tc = rd("PHX_SW_TC", 0);
-    k.sw_work_waves = rd("PHX_SW_WORK_WAVES", 0);
+    k.generic_sched = rd("PHX_GENERIC_SCHED", 1);
     return k;
   }();
-  return knobs;
+  return sw;
 }
 
 int phx_abi_version(void) { return PHX_ABI_VERSION; }
@@ -740,7 +701,7 @@ int phx_n_exo(const phx_spec* spec) { Derived d; return derive(spec, d) == PHX_O
 int phx_create(const phx_spec* spec, int device, void* state_blob, int64_t state_nbytes, phx_env** out) {
   if (!out) return fail(PHX_EINVAL, "null out");
   *out = nullptr;
-  (void)phx_knobs();                                    // the development knobs are read here, once per process
+  (void)phx_switches();                                 // the environment is read here, once per process
   phx_env* e = new phx_env();
   int rc = derive(spec, e->der);
   if (rc != PHX_OK) { delete e; return rc; }
@@ -1176,10 +1137,7 @@ int phx_step(phx_env* e, const phx_step_io* io, void* stream) {
     HIPCHK(phx_launch_stk_materialise(e->d, st));   // the table and stay on the generic engine from here on
     e->prices_compressed = false; e->use_stk = false;
   }
-  GenArgs g; memset(&g, 0, sizeof g); g.io = *io; g.inject = e->inject_dev; g.n_inject = e->n_inject; g.resolve_only = 0; g.timing = nullptr; g.roll_t = -1;
-#ifdef PHX_TIMING
-  g.timing = phx_gen_timing(1);
-#endif
+  GenArgs g; memset(&g, 0, sizeof g); g.io = *io; g.inject = e->inject_dev; g.n_inject = e->n_inject; g.resolve_only = 0; g.roll_t = -1;
   rc = upload_inject(e, st);
   if (rc != PHX_OK) return rc;
   if (e->n_inject) HIPCHK(hipStreamSynchronize(st));   // inject_host is reused right after
@@ -1205,7 +1163,7 @@ static int step_half(phx_env* e, const phx_step_io* io, void* stream, int phase)
     e->prices_compressed = false; e->use_stk = false;
   }
   GenArgs g; memset(&g, 0, sizeof g); g.io = *io; g.inject = e->inject_dev; g.n_inject = phase == 1 ? e->n_inject : 0;
-  g.resolve_only = 0; g.phase = phase; g.timing = nullptr; g.roll_t = -1;
+  g.resolve_only = 0; g.phase = phase; g.roll_t = -1;
   if (phase == 1) {
     rc = upload_inject(e, st);
     if (rc != PHX_OK) return rc;
@@ -1241,7 +1199,7 @@ int phx_resolve(phx_env* e, int32_t* err, phx_msg_rec* msg_log, int32_t* msg_cou
   }
   GenArgs g; memset(&g, 0, sizeof g);
   g.io.err = err; g.io.msg_log = msg_log; g.io.msg_count = msg_count;
-  g.inject = e->inject_dev; g.n_inject = e->n_inject; g.resolve_only = 1; g.timing = nullptr; g.roll_t = -1;
+  g.inject = e->inject_dev; g.n_inject = e->n_inject; g.resolve_only = 1; g.roll_t = -1;
   int rc = upload_inject(e, st);
   if (rc != PHX_OK) return rc;
   if (e->n_inject) HIPCHK(hipStreamSynchronize(st));
@@ -1258,7 +1216,7 @@ static int rollout_impl(phx_env* e, const phx_rollout_io* io, void* stream);
 // and the handle keeps the winner for that shape.  Both kernels produce the same bits (tests/test_gpu_fsm_sw.py), the outputs of the
 // probe launches are overwritten by the call's own.  Not while a stream is capturing (phx_fsm_sw_serves declines there already).
 static bool fsm_auto_applies(phx_env* e, const phx_rollout_io* io, void* stream) {
-  if (!phx_knobs().autotune || !e->use_fused || e->d.env_type != PHX_ENV_FSM || e->d.variant_rollout != PHX_VR_AUTO || io->policy) return false;
+  if (!phx_switches().autotune || !e->use_fused || e->d.env_type != PHX_ENV_FSM || e->d.variant_rollout != PHX_VR_AUTO || io->policy) return false;
   if (io->n_frag >= 2 && (!io->frags || !io->frags[0].terminated)) return false;
   if (io->n_frag < 2 && (io->frags || !io->obs || !io->terminated)) return false;
   return phx_fsm_sw_serves(e->d, *io, (hipStream_t)stream);
@@ -1444,16 +1402,13 @@ static int rollout_impl(phx_env* e, const phx_rollout_io* io, void* stream) {
     sio.done_valid = (uint8_t*)(base + gs.done_valid);
     sio.all_terminated = (uint8_t*)(base + gs.all_term); sio.all_truncated = (uint8_t*)(base + gs.all_trunc);
     sio.err = io->err;
-    GenArgs g; memset(&g, 0, sizeof g); g.io = sio; g.inject = e->inject_dev; g.n_inject = 0; g.resolve_only = 0; g.timing = nullptr;
+    GenArgs g; memset(&g, 0, sizeof g); g.io = sio; g.inject = e->inject_dev; g.n_inject = 0; g.resolve_only = 0;
     g.roll = *io; g.roll_actions_in = io->actions; g.roll_actions = (float*)(base + gs.actions);
     if (e->d.variant_rollout != PHX_VR_LAUNCH_LOOP) {
       // ONE launch: the kernel loops over the T steps itself (GenArgs::roll_T) -- queues, staged tables and the env's
       // workgroup stay resident; policy, trajectory row, the caller's reset and the last observation are in the loop
       sio.exo = io->exo; sio.msg_log = io->msg_log; sio.msg_count = io->msg_count;
       g.io = sio; g.roll_t = 0; g.roll_T = io->T;
-#ifdef PHX_TIMING
-      g.timing = phx_gen_timing(io->T);
-#endif
       HIPCHK(phx_launch_generic(e->d, g, e->lds_ok, st));
       return PHX_OK;
     }

@@ -51,38 +51,28 @@ struct ScFastPlan {
   int32_t ok, epb, G, K, nt, norm, whole_envs;
 };
 
-// DEVELOPMENT knobs (A/B runs of kernel variants: tools/roll_time.py, tools/gen_time.py).  They are read from the environment in ONE
-// place, once per process, at the first phx_create (phx_knobs(), phx_api.hip); the plans and launchers take them from this table --
-// no getenv in a launcher.  Per-env, supported selection of kernels is phx_spec.variant_*.
-struct DevKnobs {
-  int fsm_fast;                // PHX_FSM_FAST (default -1 = unset; 0: off; 2: forced at any batch size)
-  int fsm_lean;                // PHX_FSM_LEAN (default 1)
-  int fsm_wide;                // PHX_FSM_WIDE (default 1)
-  int fsm_batch;               // PHX_FSM_BATCH (default 1): the lean FSM rollout loop stores four steps per batch as 16-byte pieces
-  int generic_nt;              // PHX_GENERIC_NT (default 0)
-  int generic_remap;           // PHX_GENERIC_REMAP (default 1)
-  int generic_tablds;          // PHX_GENERIC_TABLDS (default 1)
+// Process-wide switches, read from the environment once per process at the first phx_create (phx_switches(), phx_api.hip).
+// Per-env selection of kernels is phx_spec.variant_*.
+struct PhxSwitches {
   int autotune;                // PHX_AUTOTUNE (default 1): PHX_VR_AUTO times its two FSM candidates on a handle's first call of a shape (0: the size rule alone)
   int generic_sched;           // PHX_GENERIC_SCHED (default 1): specs with a compiled schedule run on phx_sched_step_kernel (0: the dynamic kernel everywhere)
-  int rollout_epb;             // PHX_ROLLOUT_EPB (default 0)
-  int rollout_fast;            // PHX_ROLLOUT_FAST (default -1 = unset; 0: off)
-  int rollout_first;           // PHX_ROLLOUT_FIRST (default 0)
-  int rollout_g;               // PHX_ROLLOUT_G (default 0)
-  int rollout_ldskb;           // PHX_ROLLOUT_LDSKB (default 0)
-  int rollout_nt;              // PHX_ROLLOUT_NT (default 0)
-  int rollout_remap;           // PHX_ROLLOUT_REMAP (default -1)
-  int rollout_sparse_flags;    // PHX_ROLLOUT_SPARSE_FLAGS (default 1: round 3's kernel zero-fills the flag planes of fragments >= 2^23 agent-steps and stores the non-zero words; 0 never, 2 always)
-  int step_nt;                 // PHX_STEP_NT (default 0)
-  int stk_rollout_nt;          // PHX_STK_ROLLOUT_NT (default 0)
-  int stk_step_fast;           // PHX_STK_STEP_FAST (default 1)
-  int stk_step_nt;             // PHX_STK_STEP_NT (default 0)
-  int sw_generic;              // PHX_SW_GENERIC (default 0)
-  int sw_persist;              // PHX_SW_PERSIST (default 1): the store-wave kernel's workgroups walk several pair groups (0: one workgroup per group)
-  int sw_store_waves;          // PHX_SW_STORE_WAVES (default 0)
-  int sw_tc;                   // PHX_SW_TC (default 0)
-  int sw_work_waves;           // PHX_SW_WORK_WAVES (default 0)
 };
-const DevKnobs& phx_knobs();
+const PhxSwitches& phx_switches();
+
+// Barrier that orders LDS traffic only.  __syncthreads() also drains every outstanding global store (s_waitcnt vmcnt(0)) because
+// it is a workgroup-scope release; the rollout kernels' LDS tiles need no global visibility inside the kernel, and draining would
+// expose the HBM write latency at each barrier instead of letting the trajectory stores retire under the next chunk's work.
+__device__ __forceinline__ void phx_lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// ceil(2^32 / d): i / d == umulhi(i, phx_magic32(d)) for i < 2^16 (d > 1; the magic of 1 does not fit 32 bits)
+static inline uint32_t phx_magic32(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)(d > 0 ? d : 1)); }
+
+// 5^-k as f32, k = 0..6: the reciprocal of 5^K the rollout kernels divide by (floor(y * inv) == y / 5^K for y < 5^6)
+constexpr float inv_pow5[7] = {1.0f, 0.2f, 0.04f, 0.008f, 0.0016f, 0.00032f, 0.000064f};
 
 // workgroup shape of the round-4 store-wave rollout kernel (phx_sc_rollout_sw.hip)
 struct ScSwPlan {
@@ -242,7 +232,6 @@ struct GenArgs {               // arguments of the generic engine kernel
   int32_t resolve_only;         // Network.resolve() alone: no clock tick, no acting, no epilogue
   int32_t phase;                // 0: a whole step; 1: phx_step_begin (acting + resolve_network, no epilogue: a host-side stage handler
                                 // reads the resolved agent state next, fsm.py:294-302); 2: phx_step_end (transition + epilogue only)
-  unsigned long long* timing;   // PHX_TIMING builds only
   int32_t tab_off;              // byte offset of the LDS-staged topology tables (generic engine)
   int32_t xcd_remap;            // XCD-aware workgroup -> env mapping (xcd_block)
   // launch-loop rollout (phx_rollout on the generic engine): the policy, the trajectory row of step roll_t and
@@ -379,11 +368,8 @@ __device__ __forceinline__ int dev_send_check(const DevSpec& sp, const Topo& tp,
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t out[4]) {
   // one 32x32->64 product per multiplier and round (v_mad_u64_u32 gives hi and lo together)
-#ifndef PHX_PHILOX_ROUNDS
-#define PHX_PHILOX_ROUNDS 10
-#endif
 #pragma unroll
-  for (int r = 0; r < PHX_PHILOX_ROUNDS; ++r) {
+  for (int r = 0; r < 10; ++r) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
     // three-way xor in ONE instruction (gfx950: v_bitop3_b32, truth table 0x96); the compiler emits two v_xor_b32 otherwise
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)      /* PHX_OFFLOAD_ARCH builds for other CDNA parts: no v_bitop3_b32 */

@@ -646,9 +646,7 @@ typedef const __attribute__((address_space(4))) char* phx_kptr_t;
 static_assert(alignof(GenArgs) == 8 && sizeof(const DevSpec*) == 8, "kernarg layout: (spec pointer, GenArgs at offset 8)");
 // ROLL: the instantiation phx_rollout launches (policy, trajectory row, the caller's reset and the T-step loop compiled in);
 // phx_step / phx_resolve run the one without that code
-#ifndef PHX_LEAN_WAVES
-#define PHX_LEAN_WAVES 6      // waves per SIMD the LEAN instantiations are compiled for (80 VGPRs: twelve two-wave workgroups per CU)
-#endif
+constexpr int PHX_LEAN_WAVES = 6;      // waves per SIMD the LEAN instantiations are compiled for (80 VGPRs: twelve two-wave workgroups per CU)
 // LEAN (two-wave supply chains whose acting lists all have a static schedule): order / slot / scanbuf -- the scratch only a DYNAMIC
 // step sorts and scans in -- live in the env's workspace in the blob instead of LDS: 11.5 instead of 14.6 KB per SC256 env
 // The engine for ONE env instance b, by the calling workgroup of NT threads (whole steps, halves, bare resolves, the T-step loop): the
@@ -660,15 +658,6 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
 
   __shared__ int wave_sums[NT / 64];
   __shared__ int s_errkey, s_nterm, s_ntrunc, s_dyn;
-#ifdef PHX_TIMING
-  __shared__ unsigned long long gtm[17];
-  if (threadIdx.x < 17) gtm[threadIdx.x] = 0;
-  __syncthreads();
-  if (threadIdx.x == 0) gtm[16] = wall_clock64();
-#define GTICK(k) do { PHX_REFRESH(); if (threadIdx.x == 0) { const unsigned long long now_ = wall_clock64(); gtm[k] += now_ - gtm[16]; gtm[16] = now_; } } while (0)
-#else
-#define GTICK(k) PHX_REFRESH()
-#endif
 
   const int tid = threadIdx.x;
   const int A = sp.A, S = sp.S, Q = sp.queue_cap;
@@ -783,7 +772,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     }
   }
   __syncthreads();
-  GTICK(0);
+  PHX_REFRESH();
 
   // ---- round-0 queue: host-injected sends, then the acting agents in list order -------------
   const int n_act = (full && g.phase != 2) ? sp.act_ptr[list + 1] - sp.act_ptr[list] : 0;      // (phx_step_end: acting and resolution were phx_step_begin's)
@@ -809,7 +798,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     }
     n = sch[1];
     __syncthreads();
-    GTICK(3);
+    PHX_REFRESH();
   } else {
   // per-item message counts -> exclusive scan -> queue offsets (scanbuf holds scan_cap >= n_items)
   for (int it = tid; it < n_items; it += NT) {
@@ -829,7 +818,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     scanbuf[it] = c;
   }
   __syncthreads();
-  GTICK(1);
+  PHX_REFRESH();
   n = block_exscan<NT>(scanbuf, n_items, wave_sums);
   if (n > Q) { if (tid == 0) set_errkey(&s_errkey, n_items, PHX_ERR_QUEUE_FULL); n = 0; }
   else {
@@ -851,7 +840,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     }
   }
   __syncthreads();
-  GTICK(2);
+  PHX_REFRESH();
   // acting-phase sends are checked like any Network.send (static topologies always pass)
   for (int i = tid; i < n; i += NT) {
     const DevMsg m = q0[i];
@@ -859,7 +848,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     if (code) { set_errkey(&s_errkey, g.n_inject + i, code); q0[i].type = 0; }
   }
   __syncthreads();
-  GTICK(3);
+  PHX_REFRESH();
   }   // dynamic acting phase
 
   // pre_message_resolution for every live agent (env.py:170-173)
@@ -878,7 +867,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
   int clock = clock0;
   int shuf_off = 0;             // messages of the step's earlier rounds (index into the replayed shuffle stream)
   __syncthreads();
-  GTICK(4);
+  PHX_REFRESH();
 
   // ---- BatchResolver.resolve round loop (resolvers.py:128-163) ---------------------------------
   DevMsg* qc = q0; DevMsg* qn = q1;
@@ -898,35 +887,35 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
       next_off = ord + n;
       sch_pos += 2 * A + 2 * n;
       __syncthreads();
-      GTICK(9);
+      PHX_REFRESH();
     } else {
     for (int a = tid; a < A; a += NT) { cnt[a] = 0; first[a] = 0x7fffffff; }
     __syncthreads();
-    GTICK(5);
+    PHX_REFRESH();
     for (int i = tid; i < n; i += NT) {
       const int d = qc[i].dst;
       slot[i] = atomicAdd(&cnt[d], 1);
       atomicMin(&first[d], i);
     }
     __syncthreads();
-    GTICK(6);
+    PHX_REFRESH();
     // receivers in dict (first-arrival) order -> inbox offsets
     for (int i = tid; i < n; i += NT) {
       const int d = qc[i].dst;
       scanbuf[i] = (first[d] == i) ? cnt[d] : 0;
     }
     __syncthreads();
-    GTICK(7);
+    PHX_REFRESH();
     block_exscan<NT>(scanbuf, n, wave_sums);
     for (int i = tid; i < n; i += NT) {
       const int d = qc[i].dst;
       if (first[d] == i) goff[d] = scanbuf[i];
     }
     __syncthreads();
-    GTICK(8);
+    PHX_REFRESH();
     for (int i = tid; i < n; i += NT) order[goff[qc[i].dst] + slot[i]] = i;
     __syncthreads();
-    GTICK(9);
+    PHX_REFRESH();
     // ---- batches in send order.  The slots the atomics handed out are in ARRIVAL order, which is not deterministic:
     //      message i takes the rank of its sequence number among its receiver's batch (c independent LDS reads per
     //      message, whatever the batch length -- the factory of SC256 receives 51 requests, an exchange 120 bids; round 1
@@ -1042,7 +1031,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
       if (cached) store_state(sp, r, st);
     }
     __syncthreads();
-    GTICK(10);
+    PHX_REFRESH();
     int n_next;
     if (sched_round) {                                          // scheduled round: the replies' offsets are static (no scan)
       n_next = round + 1 < sch_R ? sch[2 + round] : 0;
@@ -1075,7 +1064,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
       }
     }
     __syncthreads();
-    GTICK(11);
+    PHX_REFRESH();
     log_n += n_next; seq_base += n; clock += n; shuf_off += n;
     n = n_next; ++round;
     DevMsg* tq = qc; qc = qn; qn = tq;
@@ -1123,7 +1112,7 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
     }
   }
   __syncthreads();
-  GTICK(12);
+  PHX_REFRESH();
 
   if (tid == 0) {
     fld<int32_t>(sp, F_ENV_CLOCK)[b] = clock;
@@ -1132,12 +1121,12 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
   }
   if (g.resolve_only || g.phase == 1) return;      // (phx_step_begin stops here: the env's step counter and tick stay, the epilogue is phx_step_end's)
 
-  GTICK(13);
+  PHX_REFRESH();
   int all_flags = 0;
   const bool row_done = strategic_epilogue<NT>(sp, tp, g.io, b, t, list, cur_stage, tick, live, &s_nterm, &s_ntrunc, next_in,
                                                ROLL && roll_t >= 0 ? &g.roll : nullptr, ((int64_t)(roll_t >= 0 ? roll_t : 0) * sp.B + b) * S, &all_flags);
   all_flags = __builtin_amdgcn_readfirstlane(all_flags);
-  GTICK(14);
+  PHX_REFRESH();
   if (ROLL && roll_t >= 0) {                                   // the step's outputs -> trajectory row roll_t
     const phx_step_io& st = g.io; const phx_rollout_io& io = g.roll;
     const uint8_t at = (uint8_t)(all_flags & 1), au = (uint8_t)((all_flags >> 1) & 1);
@@ -1166,9 +1155,6 @@ __device__ __forceinline__ void phx_generic_env(phx_kptr_t spc, phx_kptr_t kp, c
   }
   __syncthreads();                                             // the next step reads the words and the state this one wrote
   }   // steps of the launch
-#ifdef PHX_TIMING
-  if (g.timing && threadIdx.x == 0 && blockIdx.x < 64) for (int q = 0; q < 16; ++q) atomicAdd(&g.timing[q], gtm[q]);
-#endif
 }
 
 // one env instance per workgroup
@@ -1216,7 +1202,7 @@ static hipError_t launch_generic_dynamic(const DevSpec& sp, const GenArgs& g_, b
 // T-step rollout loops on phx_sched_step_kernel (whose tail workgroups step the envs it flags on the dynamic engine, same launch).  Everything else -- injected sends, bare resolves, the two halves of a split step, replayed shuffles, the
 // one-launch-per-step loop, every other kind -- is the dynamic kernel's.
 hipError_t phx_launch_generic(const DevSpec& sp, const GenArgs& g_, bool lds, hipStream_t st) {
-  if (sp.gs_ok && phx_knobs().generic_sched && sp.variant_step != PHX_VS_GENERIC_DYNAMIC && g_.phase == 0 && !g_.resolve_only && g_.n_inject == 0 &&
+  if (sp.gs_ok && phx_switches().generic_sched && sp.variant_step != PHX_VS_GENERIC_DYNAMIC && g_.phase == 0 && !g_.resolve_only && g_.n_inject == 0 &&
       !g_.io.shuffle && (g_.roll_t < 0 || g_.roll_T > 0)) {
     const GenArgs& g = g_;
     return phx_launch_sched(sp, g, st);
@@ -1229,26 +1215,23 @@ static hipError_t launch_generic_dynamic(const DevSpec& sp, const GenArgs& g_, b
   const bool lean = lds && sp.lean_lds != 0;
   size_t bytes = (phx_generic_queue_bytes(sp.A, sp.S, sp.queue_cap, sp.scan_cap, sp.n_adx, lean) + 15) & ~(size_t)15;
   const size_t tab = phx_generic_table_bytes(sp.A, sp.nnz);
-  const int tablds_env = phx_knobs().generic_tablds;
   // Staging the topology tables in LDS saves latency per lookup but costs occupancy: every workgroup of the CU holds its
   // own copy.  Worth it only while queues + tables stay small (SC64: 6 KB); at SC256 (15.5 KB of queues + 10.5 KB of
   // tables = 6 workgroups per CU with them, 10 without) leaving them in global memory is 18 % faster (144 -> 118 us).
-  const bool tablds = lds && !lean && tablds_env && (tablds_env > 1 || bytes + tab <= 10 * 1024) && tab <= 24 * 1024 && bytes + tab <= 60 * 1024;
+  const bool tablds = lds && !lean && bytes + tab <= 10 * 1024 && tab <= 24 * 1024 && bytes + tab <= 60 * 1024;
   g.tab_off = (int32_t)bytes;
   // one env per workgroup writes ~100-byte output segments: with consecutive envs on one XCD their shared cache
   // lines merge in one L2 (SC64 38.6 -> 37.1 us, SC256-FSM 352 -> 343 us per step)
-  const int remap_env = phx_knobs().generic_remap;
-  g.xcd_remap = remap_env;
+  g.xcd_remap = 1;
   if (tablds) bytes += tab;
   // threads per env: one wave while the agents fit it (the barriers of a single-wave workgroup are
   // free and a CU holds sixteen of them), two waves for wider envs.  Measured at 64 / 128 / 256:
   // SC64 B=4096 40 / 63 / 94 us per step, SC256-FSM B=8192 819 / 727 / 743 us.  (Keeping the env's
   // agent state in LDS for the step was measured too: no gain, the wave is instruction-bound --
   // about 6 000 instructions and 90 memory operations per env-step at SC64.)
-  const int nt_env = phx_knobs().generic_nt;      // development: 64 or 128
   // round 2, after the factory's serial chain went message-parallel: SC256-FSM B=8192 199 / 165 / 149 us per step
   // (with the second queue gone -- 6 instead of 5 workgroups per CU -- 128 threads win again: 144 vs 177 us)
-  int nt = nt_env ? nt_env : (sp.A <= 64 ? 64 : 128);
+  const int nt = sp.A <= 64 ? 64 : 128;
   // a spec whose kinds are all supply-chain kinds (FACTORY / SHOP / CUSTOMER = 1..3) runs the instantiation that compiles
   // only their handlers (fewer registers, no exchange / market code in the round loop)
   int kmax = 0;

@@ -17,9 +17,6 @@
 #include "phx_dev.h"
 #include "phx_sc_fast.h"
 
-#ifndef PHX_STEP_REMAP
-#define PHX_STEP_REMAP 1     // XCD-aware env mapping: SC256-FSM B=8192 step 12.0 -> 10.9 us, SC64 B=65536 13.3 -> 12.7 us, neutral at B=4096 (graph replay)
-#endif
 #include <cstdlib>
 #include <cstdio>
 #include <vector>
@@ -63,7 +60,8 @@ __global__ __launch_bounds__(NT) void phx_sc_step_kernel(const DevSpec sp, const
   // must sit in one workgroup with a barrier between the two.
   extern __shared__ __attribute__((aligned(16))) unsigned char s_exo[];
   const int nS = sp.S;
-  const int64_t b_first = (int64_t)xcd_block(stage_exo >= 0 && PHX_STEP_REMAP) * epb;
+  // XCD-aware env mapping: SC256-FSM B=8192 step 12.0 -> 10.9 us, SC64 B=65536 13.3 -> 12.7 us, neutral at B=4096 (graph replay)
+  const int64_t b_first = (int64_t)xcd_block(stage_exo >= 0) * epb;
   const int64_t b_end = (b_first + epb < sp.B) ? b_first + epb : sp.B;
   const int lanes = (int)(b_end - b_first) * nS;
   const bool active = (int)threadIdx.x < lanes;
@@ -304,7 +302,6 @@ struct RollArgs {
   int32_t B, S, n_exo, num_steps, T, epb, TC, n_tabn, n_quot;
   int32_t xcd_remap;
   const float* sc_tab;
-  unsigned long long* timing;    // PHX_TIMING builds only: [blocks][8] cycle sums per phase
   uint32_t mF;                   // ceil(2^32 / (G / 4)): i / (G / 4) == umulhi(i, mF) for i < 2^16 (G > 4)
   uint64_t seed; int64_t env_offset;
   const int32_t* shop_norm;      // [S] max_sales_per_step of each shop
@@ -315,33 +312,17 @@ struct RollArgs {
   phx_rollout_io io;
 };
 
-// Barrier that orders LDS traffic only.  __syncthreads() also drains every outstanding global
-// store (s_waitcnt vmcnt(0)) because it is a workgroup-scope release; the tiles below need no
-// global visibility inside the kernel, and draining would expose the HBM write latency at each
-// barrier instead of letting the trajectory stores retire under the next chunk's Philox work.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // REPLAY: actions and/or exogenous draws come from HBM (parity / replay); false = pure device RNG.
 // WIDE:   every block owns exactly epb envs and every tile row is 16-byte aligned (host-checked),
 //         so the output phase writes whole 16-byte segments with magic-number row arithmetic only.
 template <int NT, bool REPLAY, bool WIDE>
-__global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 6 : (NT == 320 ? 5 : 4)))) void phx_sc_rollout_kernel(const RollArgs a) {
+__global__ __launch_bounds__(NT, NT == 384 ? 6 : (NT == 320 ? 5 : 4)) void phx_sc_rollout_kernel(const RollArgs a) {
   if (a.only_if && *a.only_if != a.gen) return;   // (uniform) the store-wave kernel served this call
   // Software pipeline over chunks of TC steps.  Phase 1 (Philox draws) of chunk c + 1 does not
   // depend on the stock recurrence, so it runs on waves P1W.. while waves 0..P2W-1 walk the
   // recurrence (phase 2) of chunk c; item tiles {R|stock, D, sales} and the action tile are
   // double-buffered in LDS.  Per chunk:   [P2(c) || P1(c+1)]  bar  P3(c)  bar
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PHX_TIMING
-  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define TICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tm[k] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define TICK(k) do {} while (0)
-#endif
   const phx_rollout_io& io = a.io;
   const int nS = a.S, tid = threadIdx.x, TC = a.TC;
   const int64_t total = (int64_t)a.B * nS;
@@ -396,12 +377,11 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 
   // others phase 1 (when no wave is left over, everybody does phase 1 after phase 2)
   const int p2_threads = ((G + 63) >> 6) << 6;
   const int p1_first = (p2_threads + 64 <= NT) ? p2_threads : 0;
-  lds_barrier();
+  phx_lds_barrier();
   // row quads per chunk: one more when the chunk starts are not quad-aligned for every env (some
   // tick counter, or the chunk length, is not a multiple of 4)
   int quad_extra = (TC & 3) != 0;
   for (int bl = 0; bl < nb; ++bl) quad_extra |= (s_tick0[bl] & 3) != 0;
-  TICK(0);
 
   // ---- phase 1 of the chunk starting at step t0 (tc rows) into buffer `buf`, by threads
   //      [first, NT).  One Philox block serves the four ticks (4q .. 4q + 3) of a shop, so the flat
@@ -473,7 +453,7 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 
   };
 
   phase1(0, a.T < TC ? a.T : TC, 0, 0);
-  TICK(1); lds_barrier(); TICK(2);
+  phx_lds_barrier();
   int buf = 0;
   for (int t0 = 0; t0 < a.T; t0 += TC, buf ^= 1) {
     const int tc = (a.T - t0 < TC) ? a.T - t0 : TC;
@@ -483,12 +463,10 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 
     const int t1 = t0 + TC, tc1 = (a.T - t1 < TC) ? a.T - t1 : TC;     // next chunk
     // ---- phase 2: the stock recurrence, one lane per pair ---------------------------------------
     if (tid < G) {
-#ifndef PHX_NO_P2_PRIO
       // the recurrence is a dependent chain on ONE wave while the three other waves of its SIMD issue Philox
       // work: at equal priority it gets every fourth issue slot (measured 212 cycles per step); raised, it
       // issues as soon as its operands are ready and the draw waves fill the gaps
       __builtin_amdgcn_s_setprio(3);
-#endif
       // A lone wave issues about one instruction every 4-5 cycles, so this phase costs
       // (instructions per step) x T: the loop body is kept to two LDS instructions and seven
       // VALU ops.  stock' = min(max(x - D, 0) + min(R, 100 - x), 100); sales = x - max(x - D, 0).
@@ -527,14 +505,11 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 
       st.stock = x; st.sales = sales; st.missed = hasK ? Dl - sales : 0; st.delivered = req;
       step += tc;
       if (tend >= 0 && tend < tc) step -= a.num_steps;
-#ifndef PHX_NO_P2_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
     }
-    TICK(3);
     // ---- phase 1 of the NEXT chunk, overlapped with the recurrence above -------------------------
     if (t1 < a.T) phase1(t1, tc1, buf ^ 1, p1_first);
-    TICK(1); lds_barrier(); TICK(4);
+    phx_lds_barrier();
     // ---- phase 3: observations / rewards / flags straight to HBM ------------------------------------
     // WIDE: a work unit is 4 consecutive pairs of one tile row: 12 observation floats, 4 rewards,
     // 4 actions and 4 + 4 flag bytes, i.e. whole 16-byte (4-byte for the flags) segments of the
@@ -599,11 +574,8 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : (NT >= 768 ? 6 : (NT == 384 ? 
         if (gl >= G) { gl -= G; ++tl; }
       }
     }
-    TICK(6); lds_barrier(); TICK(7);
+    phx_lds_barrier();
   }
-#ifdef PHX_TIMING
-  if (a.timing && (tid & 63) == 0) for (int q = 0; q < 8; ++q) a.timing[((int64_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 8 + q] = tm[q];
-#endif
   if (tid < G) {
     const int64_t g = g_base + tid;
     const int s = tid % nS, b = (int)b_first + tid / nS;
@@ -1001,7 +973,7 @@ __global__ __launch_bounds__(SC_NT) void phx_sc_rollout_fsm_lean_kernel(const De
 // ---- launchers ------------------------------------------------------------------------------------
 hipError_t phx_launch_sc_step(const DevSpec& sp, const phx_step_io& io, hipStream_t st) {
   // whole envs per block (S <= 256 checked at create).  64-, 128- and 256-thread blocks time the
-  // same (the per-launch mode is bound by the host's launch cadence); PHX_STEP_NT overrides.
+  // same (the per-launch mode is bound by the host's launch cadence): 256.
   // large plain batches: four pairs per thread (AUTO from 2^19 pairs per launch up -- SC64: B = 65 536 9.8 -> 9.6 us, 131 072 19.4 -> 14.3,
   // 262 144 35.9 -> 24.9; PHX_VS_WIDE forces it wherever it applies)
   // (its 16- and 4-byte accesses want the caller's planes aligned like torch / hipMalloc allocations are; anything else: the lane-per-pair kernel)
@@ -1025,18 +997,13 @@ hipError_t phx_launch_sc_step(const DevSpec& sp, const phx_step_io& io, hipStrea
       return hipGetLastError();
     }
   }
-  int nt = 256;
-  const int force_nt = phx_knobs().step_nt;
-  if (force_nt == 64 || force_nt == 128 || force_nt == 256) nt = force_nt < sp.S ? 256 : force_nt;
-  const int epb = nt / sp.S;
+  const int epb = 256 / sp.S;
   const int blocks = (sp.B + epb - 1) / epb;
   const int64_t bytes = (int64_t)epb * sp.n_exo + 32;
   const int stage = (io.exo && bytes <= SC_STAGE_MAX) ? 1 : 0;
   const size_t lds = stage ? (size_t)bytes : 0;
   phx_note_kernel("phx_sc_step_kernel");
-  if (nt == 64) hipLaunchKernelGGL((phx_sc_step_kernel<64>), dim3(blocks), dim3(64), lds, st, sp, io, epb, stage);
-  else if (nt == 128) hipLaunchKernelGGL((phx_sc_step_kernel<128>), dim3(blocks), dim3(128), lds, st, sp, io, epb, stage);
-  else hipLaunchKernelGGL((phx_sc_step_kernel<256>), dim3(blocks), dim3(256), lds, st, sp, io, epb, stage);
+  hipLaunchKernelGGL((phx_sc_step_kernel<256>), dim3(blocks), dim3(256), lds, st, sp, io, epb, stage);
   return hipGetLastError();
 }
 
@@ -1063,8 +1030,7 @@ static bool phx_sc_fsm_static(const DevSpec& sp, const phx_rollout_io& io) {
 
 hipError_t phx_launch_sc_rollout_fsm(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st, const int32_t* only_if_in, int32_t gen_in) {
   const int epb = SC_NT / sp.S;
-  const int remap_env = phx_knobs().rollout_remap;
-  const int remap = remap_env >= 0 ? remap_env : 1;
+  const int remap = 1;                    // XCD-aware workgroup -> env mapping (xcd_block)
   // store-wave / time-parallel kernel first where a plan applies; the lane-per-pair loop below then runs only if that kernel found
   // an env off the tabulated stage chain (a stage a handler or the caller set) and left the launch alone
   const int32_t* only_if = only_if_in; int32_t gen = gen_in;
@@ -1079,16 +1045,13 @@ hipError_t phx_launch_sc_rollout_fsm(const DevSpec& sp, const phx_rollout_io& io
     hipError_t fe = hipSuccess;
     if (phx_launch_sc_rollout_fsmfast(sp, io, st, &fe, &gen)) { if (fe != hipSuccess) return fe; only_if = sp.fsm_irregular; }
   }
-  const int lean_env = phx_knobs().fsm_lean;      // development default
-  const bool lean = vr == PHX_VR_LEAN || (vr != PHX_VR_GENERAL && lean_env);
+  const bool lean = vr != PHX_VR_GENERAL;
   if ((lean || only_if) && sp.fsm_lean_K > 0 && sp.env_type == PHX_ENV_FSM && !io.actions && !io.exo && sp.n_samplers == 0) {
     uint32_t pk = 1; for (int k = 0; k < sp.fsm_lean_K; ++k) pk *= 5u;
-    static const float inv[7] = {1.0f, 0.2f, 0.04f, 0.008f, 0.0016f, 0.00032f, 0.000064f};
-    // blocks that start on multiples of 4 pairs (16-byte aligned observation rows): whole envs, a multiple of 4 of them
+      // blocks that start on multiples of 4 pairs (16-byte aligned observation rows): whole envs, a multiple of 4 of them
     // unless the shop count is one itself
     int epb_l = epb; int wide = 0;
-    const int wide_env = phx_knobs().fsm_wide;
-    if (wide_env && ((int64_t)sp.B * sp.S) % 4 == 0) {
+    if (((int64_t)sp.B * sp.S) % 4 == 0) {
       if (sp.S % 4 == 0) wide = (sp.B % epb == 0);
       else if ((SC_NT / sp.S) >= 4) { const int e4 = (SC_NT / sp.S) & ~3; if (sp.B % e4 == 0) { epb_l = e4; wide = 1; } }
     }
@@ -1103,11 +1066,11 @@ hipError_t phx_launch_sc_rollout_fsm(const DevSpec& sp, const phx_rollout_io& io
     if (pairs) wide = 1;
     // four steps per store batch (16-byte pieces of every plane): blocks of consecutive pairs whose waves start on 16-pair boundaries,
     // all four u8 planes present, 32-bit offsets within a batch's four rows
-    const int batch = (pairs && phx_knobs().fsm_batch && total % 16 == 0 && io.terminated && io.obs_valid && io.reward_valid && io.T >= 4 &&
+    const int batch = (pairs && total % 16 == 0 && io.terminated && io.obs_valid && io.reward_valid && io.T >= 4 &&
                        total * 48 < ((int64_t)1 << 32)) ? 1 : 0;
     if (batch) lds += (size_t)(SC_NT / 64) * 6144 + 16;
     hipLaunchKernelGGL(phx_sc_rollout_fsm_lean_kernel, dim3(grid), dim3(SC_NT), lds, st, sp, io, epb_l, remap,
-                       pk, inv[sp.fsm_lean_K], wide, only_if, gen, pairs, batch);
+                       pk, inv_pow5[sp.fsm_lean_K], wide, only_if, gen, pairs, batch);
     return hipGetLastError();
   }
   phx_note_kernel("phx_sc_rollout_fsm_kernel");
@@ -1123,14 +1086,13 @@ hipError_t phx_launch_sc_rollout_fsm(const DevSpec& sp, const phx_rollout_io& io
 // FSM supply chains whose stage handlers are declared as rules (phx_spec.stage_rules): the lane-per-pair loop with the rules evaluated in it
 hipError_t phx_launch_sc_rollout_fsm_rules(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st) {
   const int epb = SC_NT / sp.S;
-  const int remap_env = phx_knobs().rollout_remap;
   const size_t lds = (((size_t)sp.n_lists * sp.S + 15) & ~(size_t)15) + (size_t)3 * epb * sp.n_rules * sizeof(int) + (size_t)sp.n_lists * sizeof(int) + 8 +
                      (size_t)sp.n_rules * sizeof(DevRule) + 16;
   phx_note_kernel("phx_sc_rollout_fsm_kernel[rules]");
   if (phx_sc_fsm_static(sp, io))
-    hipLaunchKernelGGL((phx_sc_rollout_fsm_kernel<true, true>), dim3((sp.B + epb - 1) / epb), dim3(SC_NT), lds, st, sp, io, epb, remap_env >= 0 ? remap_env : 1);
+    hipLaunchKernelGGL((phx_sc_rollout_fsm_kernel<true, true>), dim3((sp.B + epb - 1) / epb), dim3(SC_NT), lds, st, sp, io, epb, 1);
   else
-    hipLaunchKernelGGL((phx_sc_rollout_fsm_kernel<true, false>), dim3((sp.B + epb - 1) / epb), dim3(SC_NT), lds, st, sp, io, epb, remap_env >= 0 ? remap_env : 1);
+    hipLaunchKernelGGL((phx_sc_rollout_fsm_kernel<true, false>), dim3((sp.B + epb - 1) / epb), dim3(SC_NT), lds, st, sp, io, epb, 1);
   return hipGetLastError();
 }
 
@@ -1143,33 +1105,20 @@ hipError_t phx_launch_sc_rollout(const DevSpec& sp, const phx_rollout_io& io, hi
   a.seed = sp.seed; a.env_offset = sp.env_offset;
   a.shop_norm = sp.shop_norm; a.shop_cust_ptr = sp.shop_cust_ptr; a.shop_cust_exo = sp.shop_cust_exo;
   a.sc_tab = sp.sc_tab; a.n_tabn = sp.n_tabn; a.n_quot = sp.n_quot;
-  a.timing = nullptr;
-#ifdef PHX_TIMING
-  { static unsigned long long* tbuf = nullptr; if (!tbuf) (void)hipMalloc((void**)&tbuf, 8 * 8 * 8192 * sizeof(unsigned long long)); a.timing = tbuf;
-    if (getenv("PHX_TIMING_DUMP")) { static int calls = 0; if (++calls == 20) { (void)hipDeviceSynchronize(); std::vector<unsigned long long> h(8 * 8 * 8192); (void)hipMemcpy(h.data(), tbuf, h.size() * 8, hipMemcpyDeviceToHost);
-      const int nw = ((sp.B + 7) / 8) * 8; double sum[8] = {0}; double w0[8] = {0}; for (int w = 0; w < nw; ++w) for (int q = 0; q < 8; ++q) { sum[q] += h[(size_t)w * 8 + q]; if (w % 8 == 0) w0[q] += h[(size_t)w * 8 + q]; }
-      fprintf(stderr, "PHX_TIMING avg cycles per wave: setup %.0f | P1 %.0f | bar %.0f | P2 %.0f | bar %.0f | P3a %.0f | P3b(+bar) %.0f | bar %.0f\n", sum[0]/nw, sum[1]/nw, sum[2]/nw, sum[3]/nw, sum[4]/nw, sum[5]/nw, sum[6]/nw, sum[7]/nw);
-      fprintf(stderr, "PHX_TIMING wave0 of each block:      setup %.0f | P1 %.0f | bar %.0f | P2 %.0f | bar %.0f | P3a %.0f | P3b(+bar) %.0f | bar %.0f\n", w0[0]*8/nw, w0[1]*8/nw, w0[2]*8/nw, w0[3]*8/nw, w0[4]*8/nw, w0[5]*8/nw, w0[6]*8/nw, w0[7]*8/nw); } } }
-#endif
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES];
   a.missed = (int32_t*)sp.f[F_SHOP_MISSED]; a.delivered = (int32_t*)sp.f[F_SHOP_DELIVERED];
   a.env_step = (int32_t*)sp.f[F_ENV_STEP]; a.env_tick = (int32_t*)sp.f[F_ENV_TICK];
   a.io = io;
   // whole envs per block: a multiple of 4 so that G = epb * S makes every tile row a 16-byte
   // multiple; B = 4096, S = 9 -> epb 4, G 36, 1024 blocks of 256 threads
-  int epb = 0;
-  const int force_epb = phx_knobs().rollout_epb;
-  if (force_epb > 0 && force_epb * sp.S <= 256 && force_epb <= sp.B) epb = force_epb;
   // measured best on SC64 and SC256 up to ~100 k pairs: 256-thread blocks owning ~32..64 pairs;
   // beyond that (the chip is full either way) 512-thread blocks with twice the pairs win by ~5 %
   const bool big = (int64_t)sp.B * sp.S >= 131072 && 8 * sp.S <= 256;
-  if (!epb && big) epb = 8;
+  int epb = big ? 8 : 0;
   if (!epb) for (int cand = 4; cand * sp.S <= 256 && cand <= sp.B; cand += 4) if (cand * sp.S >= 32) { epb = cand; break; }
   if (!epb) { epb = 256 / sp.S; if (epb > 4) epb &= ~3; if (epb < 1) epb = 1; if (epb > sp.B) epb = sp.B; }
   const int G = epb * sp.S;
-  auto magic = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)(d > 0 ? d : 1)); };
-  const int ldskb_env = phx_knobs().rollout_ldskb;
-  const int ldskb = ldskb_env ? ldskb_env : (big ? 44 : 30);
+  const int ldskb = big ? 44 : 30;
   int TC = (ldskb * 1024) / (G * 32); if (TC < 1) TC = 1; if (TC > io.T) TC = io.T;   // 32 B of LDS per item (double-buffered tiles)
   while ((int64_t)TC * G * 3 >= 65536 && TC > 1) --TC;          // magic division range
   if (sp.num_steps >= 1 && TC > sp.num_steps) TC = sp.num_steps; // at most one episode end per chunk
@@ -1185,7 +1134,7 @@ hipError_t phx_launch_sc_rollout(const DevSpec& sp, const phx_rollout_io& io, hi
     }
     TC = best;
   }
-  a.mF = magic(G / 4);
+  a.mF = phx_magic32(G / 4);
   const int items = TC * G;
   const size_t lds = (size_t)((items + 3) & ~3) * 4 * 3 * 2 + (size_t)((items + 3) & ~3) * 4 * 2 +
                      (size_t)((G + 3) & ~3) * 4 + (size_t)((epb + 3) & ~3) * 12 + (size_t)((sp.S + 4) & ~3) * 4 +
@@ -1193,14 +1142,12 @@ hipError_t phx_launch_sc_rollout(const DevSpec& sp, const phx_rollout_io& io, hi
   a.epb = epb; a.TC = TC;
   // XCD-aware workgroup -> env mapping (xcd_block).  Measured, SC64, T = 100, back-to-back launches: HBM write
   // traffic 90.8 -> 80.8 MB per launch at B = 4096 (the algorithmic 82.3 MB); +1 % at B = 4096, +5 % at 16384,
-  // +8 % at 65536.  PHX_ROLLOUT_REMAP = 0 identity, 1 contiguous eighths, n > 1 locality groups of n workgroups.
-  const int remap_env = phx_knobs().rollout_remap;
-  a.xcd_remap = remap_env >= 0 ? remap_env : 1;
+  // +8 % at 65536.  (The kernel also takes 0 = identity and n > 1 = locality groups of n workgroups; 1 = contiguous eighths.)
+  a.xcd_remap = 1;
   const dim3 grid((sp.B + epb - 1) / epb);
   const bool replay = io.actions != nullptr || io.exo != nullptr;
   const int64_t total = (int64_t)sp.B * sp.S;
   const bool wide = (sp.B % epb == 0) && (G % 4 == 0) && (total % 4 == 0);
-  const int nt_env = phx_knobs().rollout_nt;
   // block size: the waves that hold a recurrence lane + enough waves to take phase 1 (one work item
   // per row quad and pair) in a single pass, when that fits 512 threads
   int nt = 256;
@@ -1210,7 +1157,6 @@ hipError_t phx_launch_sc_rollout(const DevSpec& sp, const phx_rollout_io& io, hi
     if (want <= 256) nt = 256; else if (want <= 320) nt = 320; else if (want <= 384) nt = 384; else if (want <= 512) nt = 512;
     else nt = big ? 512 : 256;
   }
-  if (nt_env) nt = nt_env;
   phx_note_kernel(only_if ? "phx_sc_rollout_kernel[if an action rounds below zero]" : "phx_sc_rollout_kernel");
 #define PHX_LAUNCH_ROLLOUT(NT_)                                                                              \
   do {                                                                                                        \
@@ -1219,8 +1165,7 @@ hipError_t phx_launch_sc_rollout(const DevSpec& sp, const phx_rollout_io& io, hi
     else if (!replay) hipLaunchKernelGGL((phx_sc_rollout_kernel<NT_, false, false>), grid, dim3(NT_), lds, st, a);    \
     else hipLaunchKernelGGL((phx_sc_rollout_kernel<NT_, true, false>), grid, dim3(NT_), lds, st, a);                  \
   } while (0)
-  if (nt == 1024) PHX_LAUNCH_ROLLOUT(1024); else if (nt == 768) PHX_LAUNCH_ROLLOUT(768); else if (nt == 384) PHX_LAUNCH_ROLLOUT(384);
-  else if (nt == 320) PHX_LAUNCH_ROLLOUT(320);
+  if (nt == 384) PHX_LAUNCH_ROLLOUT(384); else if (nt == 320) PHX_LAUNCH_ROLLOUT(320);
   else if (nt == 512) PHX_LAUNCH_ROLLOUT(512); else PHX_LAUNCH_ROLLOUT(256);
 #undef PHX_LAUNCH_ROLLOUT
   return hipGetLastError();

@@ -3,7 +3,7 @@
 // Same path as phx_sc_rollout_kernel (phx_sc_fused.hip): T consecutive PhantomEnv.step() calls of a
 // FACTORY / SHOP / CUSTOMER env (supply_chain.py:36-150, env.py:239-303) per launch, random policy and
 // device-RNG orders, auto-reset at episode end (the list-of-envs loop of utils/rllib/rollout.py:361-363),
-// bit-identical trajectories.  What changed is who does what.  Measured on the round-1 kernel (PHX_TIMING):
+// bit-identical trajectories.  What changed is who does what.  Measured on the round-1 kernel (cycle counters):
 // the stock recurrence -- one lane per (env, shop), sequential in time -- was the critical path of every
 // chunk: 210 cycles per step for ~21 instructions, because each of its instructions queues behind the
 // quarter-rate multiplies of the three draw waves sharing its SIMD, and the draw and output waves idled at
@@ -42,16 +42,9 @@ struct FastArgs {
   uint32_t mG, mG4, mS, mPR;        // ceil(2^32 / d) magics: i / G, i / (G / 4), i / S, i / (3 G / 4)  for i < 2^16
   int32_t norm;                     // the shops' common max_sales_per_step
   uint64_t seed; int64_t env_offset;
-  unsigned long long* timing;       // PHX_TIMING builds only
   int32_t *stock, *sales, *missed, *delivered, *env_step, *env_tick, *env_arrive;
   phx_rollout_io io;
 };
-
-__device__ __forceinline__ void fast_lds_barrier() {     // orders LDS traffic only: trajectory stores stay in flight
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // four workgroups per CU must stay co-resident (B = 4096 is ONE round of 1 024 workgroups): NT / 64 waves per SIMD
 // The arguments are read from the kernarg segment through a constant-address-space pointer whose provenance is hidden from
@@ -77,15 +70,9 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
   const int64_t b_first = a.whole_envs ? (int64_t)bid * a.epb : g_base / nS;
   const int r0 = (int)(g_base - b_first * nS);                          // the first pair's shop
   const int n_env = a.whole_envs ? a.epb : (r0 + G - 1) / nS + 1;       // envs the block touches (<= a.epb)
-#ifdef PHX_TIMING
-  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define FTICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tm[k] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define FTICK(k) do {} while (0)
-#endif
 
   // ---- LDS carve (16-byte aligned sections).  The constant tables are COMPUTED here, not loaded: 1 024 workgroups
-  //      fetching the same few cache lines at launch cost ~10 k cycles of setup (measured, PHX_TIMING) ------------
+  //      fetching the same few cache lines at launch cost ~10 k cycles of setup (measured, cycle counters) ------------
   uint32_t* s_pair = (uint32_t*)smem;                                   // [G] shop | env_local << 8
   uint8_t* s_ds = (uint8_t*)(s_pair + ((G + 3) & ~3));                  // [125] base-5 digit sum of k < 5^3
   float* s_tabs = (float*)(s_ds + 128);                                 // [101] stock / 100            encode_observation,
@@ -125,7 +112,6 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
   }
   const int quad_extra = s_flags[0];      // chunk starts are not quad-aligned for every env: one more row quad
   const bool weird = s_flags[1] != 0;     // a stock the caller set outside [0, 100] (any step brings it back into range)
-  FTICK(0);
 
   // Thread roles: the waves that hold a recurrence lane (tid < rec_threads) walk the stock recurrence and nothing
   // else after the first chunk's draws; the other waves ("workers") write the outputs of chunk c and draw chunk
@@ -134,7 +120,7 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
   // Chunks: a.first_rows rows first, then TC rows each.  (A short first chunk would start the trajectory stores
   // earlier -- nothing is stored before the first chunk is drawn and walked -- but every extra iteration costs
   // more than that buys: first_rows = 4 / 8 / 12 measured 23.3 / 23.3 / 23.5 us per launch against 21.5 us for
-  // first_rows = TC, SC64, B = 4096, T = 100.  PHX_ROLLOUT_FIRST overrides.)
+  // first_rows = TC, SC64, B = 4096, T = 100.)
   const int first_rows = a.first_rows;
   const int n_chunks = 1 + (a.T - first_rows + TC - 1) / TC;
   auto start_of = [&](int c) { return c == 0 ? 0 : first_rows + (c - 1) * TC; };
@@ -161,11 +147,7 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
       if (!aligned && (tla + 3 < 0 || tla >= tc)) continue;
       const uint32_t tick_a = tick_base + (uint32_t)tla;                 // multiple of 4
       uint32_t w[4];
-#ifdef PHX_ABL_NODRAW
-      w[0] = tick_a * 2654435761u + (uint32_t)genv; w[1] = w[0] * 40503u + s; w[2] = w[1] ^ 0x9e3779b9u; w[3] = w[2] + w[0];   // dev ablation: no Philox
-#else
       rng_block(a.seed, genv, tick_a, s, 0, 0, w);
-#endif
       // the four words of the block -> four ticks.  The accept path is branch-free so that the four items' LDS lookups
       // overlap; the redraw of a rejected word (probability 3.3e-6) is ONE cold branch after it
       uint32_t y[4], aj[4];
@@ -323,9 +305,6 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
         st[0] = make_float4(o[0], o[1], o[2], o[3]); st[1] = make_float4(o[4], o[5], o[6], o[7]); st[2] = make_float4(o[8], o[9], o[10], o[11]);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the wave's own pieces are in LDS (wave-private region: no barrier)
-#ifdef PHX_ABL_NOSTORE
-      if (a.norm != -12345) { if (u < n_units && vrw.x == 1.2345e30f) *(float4*)p_rew = vrw; continue; }   // dev ablation: everything but the stores
-#endif
       const uint32_t q0 = 3u * (uint32_t)ub, qn = 3u * (uint32_t)n_units;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -338,15 +317,11 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
       if (u < n_units) {
         *(float4*)(p_rew + (size_t)(eo * 4u)) = vrw;
         *(float4*)(p_act + (size_t)(eo * 4u)) = va;
-#ifndef PHX_ABL_NOFLAGS
         if (flags_sparse) { if (tr) *(uint32_t*)(p_tru + (size_t)eo) = tr; }       // (an episode's last row: one row in num_steps)
         else {
           *(uint32_t*)(p_tru + (size_t)eo) = tr;
           if (wr_ter) *(uint32_t*)(p_ter + (size_t)eo) = 0u;
         }
-#else
-        if (a.norm == -12345) *(uint32_t*)(p_tru + (size_t)eo) = tr;     // dev ablation: neither flag plane is stored
-#endif
       }
     }
   };
@@ -364,17 +339,12 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
     const int co = it, cr = it + 1, cd = it + 2;
     if (tid < rec_threads && it > -2) {
       if (cr < n_chunks) recurrence(cr, rows_of(cr));
-      FTICK(3);
     } else {
-      if (co >= 0) { outputs(co, start_of(co), rows_of(co)); FTICK(5); }
+      if (co >= 0) { outputs(co, start_of(co), rows_of(co)); }
       if (cd < n_chunks) draws(start_of(cd), rows_of(cd), cd % 3, it == -2 ? 0 : rec_threads);
-      FTICK(1);
     }
-    fast_lds_barrier(); FTICK(6);
+    phx_lds_barrier();
   }
-#ifdef PHX_TIMING
-  if (a.timing && (tid & 63) == 0) for (int q = 0; q < 8; ++q) a.timing[((int64_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 8 + q] = tm[q];
-#endif
   // ---- state after the fragment ---------------------------------------------------------------------------------
   if (tid < G) {
     const int64_t g = g_base + tid;
@@ -411,16 +381,11 @@ __global__ __launch_bounds__(NT, (NT > 512 ? NT / 256 : NT / 64)) void phx_sc_ro
 #undef FAST_REFRESH
 
 // ---- host: plan, blob, launcher -------------------------------------------------------------------------------------
-static uint32_t magic32(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)(d > 0 ? d : 1)); }
 
 bool phx_sc_fast_plan(int B, int S, int K_uniform, bool norm_uniform, int num_steps, int block, bool aligned, ScFastPlan* p) {
   memset(p, 0, sizeof *p);
-  const int off = (phx_knobs().rollout_fast == 0);     // development default only:
-  if (off) return false;                                                                               // per env: phx_spec.variant_rollout
   if (K_uniform < 1 || K_uniform > 6 || !norm_uniform || S < 1 || S > 255 || num_steps < PHX_FAST_TC) return false;
   const int64_t total = (int64_t)B * S;
-  const int g_env = phx_knobs().rollout_g;               // development default of variant_block
-  if (block == 0) block = g_env;
   // (the kernel's LDS -- phx_launch_sc_rollout_fast: constants + 11 tile words per item of a 20-row chunk -- has to fit the CU's 160 KB:
   //  ADVICE r4, block = 184 .. 192 planned and then failed at launch)
   auto lds_of = [&](int G) { const size_t epb_ = (size_t)((G + S - 2) / S + 1);
@@ -483,30 +448,16 @@ hipError_t phx_launch_sc_rollout_fast(const DevSpec& sp, const phx_rollout_io& i
   const ScFastPlan& p = sp.sc_fast;
   FastArgs a;
   a.B = sp.B; a.S = sp.S; a.epb = p.epb; a.G = p.G; a.whole_envs = p.whole_envs; a.K = p.K; a.T = io.T; a.num_steps = sp.num_steps;
-  const int remap_env = phx_knobs().rollout_remap;
-  a.xcd_remap = remap_env >= 0 ? remap_env : 1;
+  a.xcd_remap = 1;
   uint32_t pk = 1; for (int k = 0; k < p.K; ++k) pk *= 5u;
-  static const float inv[7] = {1.0f, 0.2f, 0.04f, 0.008f, 0.0016f, 0.00032f, 0.000064f};
-  a.pK = pk; a.inv_pK = inv[p.K];
-  a.mG = magic32(p.G); a.mG4 = magic32(p.G / 4); a.mS = magic32(sp.S); a.mPR = magic32(3 * (p.G / 4));
+  a.pK = pk; a.inv_pK = inv_pow5[p.K];
+  a.mG = phx_magic32(p.G); a.mG4 = phx_magic32(p.G / 4); a.mS = phx_magic32(sp.S); a.mPR = phx_magic32(3 * (p.G / 4));
   a.norm = p.norm; a.seed = sp.seed; a.env_offset = sp.env_offset;
-  const int first_env = phx_knobs().rollout_first;
-  int first = first_env > 0 ? first_env : PHX_FAST_TC;
-  if (first > PHX_FAST_TC) first = PHX_FAST_TC;
-  if (io.T <= PHX_FAST_TC) first = io.T;
-  a.first_rows = first;
+  a.first_rows = io.T <= PHX_FAST_TC ? io.T : PHX_FAST_TC;
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES];
   a.missed = (int32_t*)sp.f[F_SHOP_MISSED]; a.delivered = (int32_t*)sp.f[F_SHOP_DELIVERED];
   a.env_step = (int32_t*)sp.f[F_ENV_STEP]; a.env_tick = (int32_t*)sp.f[F_ENV_TICK]; a.env_arrive = (int32_t*)sp.f[F_ENV_ARRIVE];
   a.io = io;
-  a.timing = nullptr;
-#ifdef PHX_TIMING
-  { static unsigned long long* tbuf = nullptr; if (!tbuf) (void)hipMalloc((void**)&tbuf, 8 * 8 * 8192 * sizeof(unsigned long long)); a.timing = tbuf;
-    if (getenv("PHX_TIMING_DUMP")) { static int calls = 0; if (++calls == 20) { (void)hipDeviceSynchronize(); std::vector<unsigned long long> h(8 * 8 * 8192); (void)hipMemcpy(h.data(), tbuf, h.size() * 8, hipMemcpyDeviceToHost);
-      const int wpb = p.nt / 64, nw = (int)(((int64_t)sp.B * sp.S) / p.G) * wpb; double sum[8] = {0}, w0[8] = {0}; for (int w = 0; w < nw; ++w) for (int q = 0; q < 8; ++q) { sum[q] += h[(size_t)w * 8 + q]; if (w % wpb == 0) w0[q] += h[(size_t)w * 8 + q]; }
-      fprintf(stderr, "FAST_TIMING avg cycles per wave:  setup %.0f | draws %.0f | bar %.0f | P2 %.0f | bar %.0f | out %.0f | bar+setup-loads %.0f | P2 preload %.0f\n", sum[0]/nw, sum[1]/nw, sum[2]/nw, sum[3]/nw, sum[4]/nw, sum[5]/nw, sum[6]/nw, sum[7]/nw);
-      fprintf(stderr, "FAST_TIMING wave0 of each block:  setup %.0f | draws %.0f | bar %.0f | P2 %.0f | bar %.0f | out %.0f | bar+setup-loads %.0f | P2 preload %.0f\n", w0[0]*wpb/nw, w0[1]*wpb/nw, w0[2]*wpb/nw, w0[3]*wpb/nw, w0[4]*wpb/nw, w0[5]*wpb/nw, w0[6]*wpb/nw, w0[7]*wpb/nw); } } }
-#endif
   const int items = PHX_FAST_TC * p.G;
   // constants (pair table, digit sums, observation / penalty tables) + 3 draw tiles x 2 planes + 2 stock tiles +
   // 2 episode-end rows + the observation staging tile (3 floats per item) + ticks + flags
@@ -516,9 +467,8 @@ hipError_t phx_launch_sc_rollout_fast(const DevSpec& sp, const phx_rollout_io& i
   // write requests unless a neighbour's share reaches the L2 in time to merge; in the store pattern alone they cost a quarter to
   // a third of the launch (tools/ubench/ub_store9.hip: 84-89 us with them, 54-62 without).  They are all zero except the
   // episodes' last rows: a streaming fill (whole lines, ~5 us per T = 400 fragment) writes the zeros, the kernel the exceptions.
-  const int sparse_env = phx_knobs().rollout_sparse_flags;      // development
   const int64_t n_flag = (int64_t)io.T * sp.B * sp.S;
-  a.flags_sparse = (sparse_env == 2 || (sparse_env && n_flag >= ((int64_t)1 << 23))) ? 1 : 0;      // (PHX_ROLLOUT_SPARSE_FLAGS: 0 never, 1 large fragments, 2 always)
+  a.flags_sparse = n_flag >= ((int64_t)1 << 23) ? 1 : 0;                      // large fragments only
   if (a.flags_sparse) {
     phx_note_kernel("phx_zero_fill_kernel[flag planes]");
     hipError_t me;
@@ -530,9 +480,7 @@ hipError_t phx_launch_sc_rollout_fast(const DevSpec& sp, const phx_rollout_io& i
     if (me != hipSuccess) return me;
   }
   const dim3 grid((unsigned)(((int64_t)sp.B * sp.S) / p.G));
-  const int nt_env = phx_knobs().rollout_nt;
-  const int rec = ((p.G + 63) / 64) * 64;
-  const int nt = (nt_env && nt_env >= rec + 64) ? nt_env : p.nt;
+  const int nt = p.nt;
   phx_note_kernel(p.whole_envs ? "phx_sc_rollout_fast_kernel[whole_envs]" : "phx_sc_rollout_fast_kernel[pairs]");
 #define PHX_LAUNCH_FAST(NT_) hipLaunchKernelGGL((phx_sc_rollout_fast_kernel<NT_>), grid, dim3(NT_), lds, st, a)
   if (lds > 64 * 1024) {               // more than 64 KB of dynamic LDS needs the attribute (wide workgroups)

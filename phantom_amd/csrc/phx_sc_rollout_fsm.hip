@@ -38,7 +38,6 @@ struct FsmFastArgs {
   const uint32_t* pos_tab;          // [num_steps] see phx_api.hip: build_fsm_fast
   const int32_t* irregular;         // device word: == gen -> some env is off the tabulated stage chain, this kernel does nothing
   int32_t gen;                      // this launch's number (the check kernel stores it in *irregular: no clearing between launches)
-  unsigned long long* timing;       // PHX_TIMING builds only
   phx_rollout_io io;
 };
 
@@ -54,12 +53,6 @@ struct FsmFastArgs {
 #define FP_ORD(w) (((w) >> 1) & 1u)
 #define FP_OBS(w) (((w) >> 2) & 1u)
 #define FP_REW(w) (((w) >> 3) & 1u)
-
-__device__ __forceinline__ void fsm_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // per env: is its stage the one the position table holds for its step?
 __global__ void phx_fsm_regular_check_kernel(const int32_t* env_step, const int32_t* env_stage, const uint32_t* pos_tab,
@@ -99,12 +92,6 @@ __global__ __launch_bounds__(NT, NT / 64) void phx_sc_rollout_fsmfast_kernel(con
   fsm_kptr_t kp = (fsm_kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
   FSM_REFRESH();
   if (*a.irregular == a.gen) return;      // (uniform) the lane-per-pair loop takes this launch
-#ifdef PHX_TIMING
-  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define FTICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tm[k] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define FTICK(k) do {} while (0)
-#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TC = PHX_FAST_TC, LB = FSM_LB;
   const int tid = threadIdx.x, nS = a.S, G = a.G, ns = a.num_steps;
@@ -169,7 +156,6 @@ __global__ __launch_bounds__(NT, NT / 64) void phx_sc_rollout_fsmfast_kernel(con
     __syncthreads();
   }
   const int quad_extra = s_flags[0];
-  FTICK(0);
   const bool weird = s_flags[1] != 0;     // (an FSM step without action or orders leaves such a stock as it is: guarded for the whole launch)
 
   const int rec_threads = ((G + 63) >> 6) << 6;
@@ -403,17 +389,12 @@ __global__ __launch_bounds__(NT, NT / 64) void phx_sc_rollout_fsmfast_kernel(con
     const int co = it, cr = it + 1, cd = it + 2;
     if (tid < rec_threads && it > -2) {
       if (cr < n_chunks) recurrence(cr, rows_of(cr));
-      FTICK(3);
     } else {
-      if (co >= 0) { outputs(co, start_of(co), rows_of(co)); FTICK(5); }
+      if (co >= 0) { outputs(co, start_of(co), rows_of(co)); }
       if (cd < n_chunks) draws(start_of(cd), rows_of(cd), cd % 3, it == -2 ? 0 : rec_threads);
-      FTICK(1);
     }
-    fsm_lds_barrier(); FTICK(6);
+    phx_lds_barrier();
   }
-#ifdef PHX_TIMING
-  if (a.timing && (tid & 63) == 0 && blockIdx.x < 2048) for (int q = 0; q < 8; ++q) a.timing[((int64_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 8 + q] = tm[q];
-#endif
 
   // ---- state after the fragment ---------------------------------------------------------------------------------------------
   if (tid < G) {
@@ -473,8 +454,6 @@ __global__ __launch_bounds__(NT, NT / 64) void phx_sc_rollout_fsmfast_kernel(con
 #undef io
 #undef FSM_REFRESH
 
-static uint32_t fsm_magic32(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)(d > 0 ? d : 1)); }
-
 // the next launch generation of the env (see below: per env, never 0)
 int32_t phx_fsm_next_gen(const DevSpec& sp) {
   std::atomic<int32_t>* gen_host = (std::atomic<int32_t>*)sp.fsm_gen_host;
@@ -487,24 +466,21 @@ int32_t phx_fsm_next_gen(const DevSpec& sp) {
 bool phx_launch_sc_rollout_fsmfast(const DevSpec& sp, const phx_rollout_io& io_, hipStream_t st, hipError_t* err, int32_t* gen_out) {
   *err = hipSuccess;
   const ScFastPlan& p = sp.fsm_fast;
-  const int off = (phx_knobs().fsm_fast == 0);
-  if (!p.ok || off || io_.actions || io_.exo || !io_.obs_valid || !io_.reward_valid) return false;
+  if (!p.ok || io_.actions || io_.exo || !io_.obs_valid || !io_.reward_valid) return false;
   if ((int64_t)io_.T + 2 * (int64_t)sp.num_steps >= 60000) return false;       // magic division of the position
   // Measured against the lane-per-pair loop (tools/roll_time.py --fsm, us per 100-step launch, this kernel / the loop): 9 shops x
   // 4 096 envs 40 / 60, x 16 384 120 / 85, x 65 536 501 / 464; 51 shops x 2 048 envs 104 / 77, x 4 096 191 / 119, x 8 192 330-370 /
   // 204-335.  The output phase costs twice the plain kernel's (own row + looked-back row per pair, silent and observing steps
   // mixed in every wave), so this kernel only wins where the loop's one lane per pair leaves the chip underfilled.
-  const int force = phx_knobs().fsm_fast;             // development default
-  if (force < 2 && sp.variant_rollout != PHX_VR_TIME_PARALLEL && (int64_t)sp.B * sp.S > 65536) return false;
+  if (sp.variant_rollout != PHX_VR_TIME_PARALLEL && (int64_t)sp.B * sp.S > 65536) return false;
   FsmFastArgs a;
   memset(&a, 0, sizeof a);
   a.B = sp.B; a.S = sp.S; a.epb = p.epb; a.G = p.G; a.whole_envs = p.whole_envs; a.K = p.K; a.T = io_.T; a.num_steps = sp.num_steps;
   a.xcd_remap = 1;
   uint32_t pk = 1; for (int k = 0; k < p.K; ++k) pk *= 5u;
-  static const float inv[7] = {1.0f, 0.2f, 0.04f, 0.008f, 0.0016f, 0.00032f, 0.000064f};
-  a.pK = pk; a.inv_pK = inv[p.K];
-  a.mG = fsm_magic32(p.G); a.mG4 = fsm_magic32(p.G / 4); a.mS = fsm_magic32(sp.S); a.mPR = fsm_magic32(3 * (p.G / 4));
-  a.mNS = fsm_magic32(sp.num_steps);
+  a.pK = pk; a.inv_pK = inv_pow5[p.K];
+  a.mG = phx_magic32(p.G); a.mG4 = phx_magic32(p.G / 4); a.mS = phx_magic32(sp.S); a.mPR = phx_magic32(3 * (p.G / 4));
+  a.mNS = phx_magic32(sp.num_steps);
   a.norm = p.norm; a.seed = sp.seed; a.env_offset = sp.env_offset;
   a.first_rows = io_.T <= PHX_FAST_TC ? io_.T : PHX_FAST_TC;
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES];
@@ -522,14 +498,6 @@ bool phx_launch_sc_rollout_fsmfast(const DevSpec& sp, const phx_rollout_io& io_,
   const int32_t launch_gen = phx_fsm_next_gen(sp);
   a.gen = launch_gen; *gen_out = launch_gen;
   a.io = io_;
-  a.timing = nullptr;
-#ifdef PHX_TIMING
-  { static unsigned long long* tbuf = nullptr; if (!tbuf) (void)hipMalloc((void**)&tbuf, 8 * 8 * 2048 * sizeof(unsigned long long)); a.timing = tbuf;
-    if (getenv("PHX_TIMING_DUMP")) { static int calls = 0; if (++calls == 20) { (void)hipDeviceSynchronize(); static unsigned long long h[8 * 8 * 2048]; (void)hipMemcpy(h, tbuf, sizeof h, hipMemcpyDeviceToHost);
-      const int wpb = p.nt / 64, nw = 2048 * wpb; double sum[8] = {0}, w0[8] = {0}; for (int w = 0; w < nw; ++w) for (int q = 0; q < 8; ++q) { sum[q] += h[(size_t)w * 8 + q]; if (w % wpb == 0) w0[q] += h[(size_t)w * 8 + q]; }
-      fprintf(stderr, "FSMF_TIMING avg cycles per wave:  setup %.0f | draws %.0f | rec %.0f | out %.0f | bar %.0f\n", sum[0]/nw, sum[1]/nw, sum[3]/nw, sum[5]/nw, sum[6]/nw);
-      fprintf(stderr, "FSMF_TIMING wave0 of each block:  setup %.0f | draws %.0f | rec %.0f | out %.0f | bar %.0f\n", w0[0]*wpb/nw, w0[1]*wpb/nw, w0[3]*wpb/nw, w0[5]*wpb/nw, w0[6]*wpb/nw); } } }
-#endif
   const int G4p = (p.G + 3) & ~3, items = PHX_FAST_TC * p.G, epb4 = (p.epb + 3) & ~3;
   const size_t lds = (size_t)G4p * 4 + 128 + 104 * 4 + 32 * 4 + 102 * 8 + (size_t)items * 4 * (6 + 2 + 3) + (size_t)G4p * 4 * 4 +
                      (size_t)3 * FSM_LB * G4p * 8 + (size_t)G4p * 4 * 5 + (size_t)((sp.num_steps + 3) & ~3) * 4 + (size_t)epb4 * 8 + 32;

@@ -24,10 +24,6 @@
 // LDS: 10 bytes per item of tiles + 32 of staging (double-buffered) instead of 44 + nothing staged.
 // Round 5: fragment lists, several pair groups per workgroup, the REPLAY (MODE 1) and FSM (MODE 2) instantiations, the workers' fused
 // phase, one store piece per trip.
-// Development macros (never defined in the product build; tools/build_variant.py / scratch variants): PHX_TIMING, PHX_RT_ONLY, PHX_RT_FILL
-// (cycle and wall-clock stamps per role), PHX_ABL_NODRAW / PHX_ABL_NOSTORE, SW_ABL_NODTAB / SW_ABL_NORTAB (LDS bank-conflict attribution),
-// SWF_ABL_NOTRACK / NOFLAGS / PLAINREC / NOPW (what each part of the FSM instantiation costs), SW_NO_FIXED_DRAWS / SW_NO_FIXED_OUT /
-// SW_NO_FUSED_WORK, SW_STORE_DEPTH.
 #include "phx_dev.h"
 #include "phx_sc_fast.h"
 
@@ -64,8 +60,6 @@ struct SwArgs {
   const uint16_t* fsm_tab;              // [2][num_steps]: the SWF_* word of every episode position, then the stage it runs in
   int32_t *env_stage, *env_prev_stage;
   double* rew_cache; uint8_t* rew_cache_v; float* obs_cache; uint8_t* obs_cache_v;      // self._rewards / self._observations (fsm.py:334-350)
-  unsigned long long* timing;           // PHX_TIMING builds only
-  unsigned long long* rt; int32_t launch_idx;   // PHX_TIMING builds only: 100 MHz wall-clock stamps per workgroup and launch
 };
 // The word of an episode position p (the step that takes the env from step p to p + 1) in the stage the chain runs it in: the stage's
 // flags at the bits they have in the tile word, and the masks of the operands it switches off (no action: R = 0, no orders: D = 0) --
@@ -86,24 +80,12 @@ struct SwArgs {
 #define SWF_RW_CACHED 0x400  /* in the lane's running index: set by a rewarded step of the episode (bit 27 of the s_fo word, unused there) */
 #define SWF_FO_LAUNCH (1u << 26)
 
-__device__ __forceinline__ void sw_lds_barrier() {       // orders LDS traffic only: the trajectory stores stay in flight
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // LDS bytes of a workgroup (host and device agree through this one function)
-// copies of the observation tables (one per LDS bank of a 32-lane group; development: SW_NC48 = 16 halves them for the 48-pair shape, whose
-// workgroup then fits a CU twice -- tools/build_variant.py; product build: 32 everywhere)
-#ifndef SW_NC48
-#define SW_NC48 32
-#endif
-__host__ __device__ inline int sw_ncopy(int G) { return G == 48 ? SW_NC48 : 32; }
 __host__ __device__ inline size_t sw_lds_bytes(int G, int epb, int TC, int dtab_n, int fsm_ns = 0) {
   const size_t G4p = (size_t)((G + 3) & ~3), items = (size_t)TC * G;
   const size_t fsm = fsm_ns > 0 ? items * 2 * 2 + G4p * 4 + (size_t)((G + 15) & ~15) + (size_t)((epb + 3) & ~3) * 4 + (size_t)((2 * fsm_ns + 15) & ~15) : 0;   // (FSM sections, below)
   return fsm + G4p * 4 + (size_t)((epb + 3) & ~3) * 4 + 16            // pair table, ticks, flags
-       + (size_t)(101 + 32) * sw_ncopy(G) * 4 + 401 * 8 * 4 + 128  // observation tables (32 copies), reward table (8 copies), digit sums of k < 125
+       + (size_t)(101 + 32) * 32 * 4 + 401 * 8 * 4 + 128           // observation tables (32 copies), reward table (8 copies), digit sums of k < 125
        + 15632                                                   // order sums of y < 5^K (5^6 reserved: the tables sit at fixed offsets)
        + items * 2 * 3 + items * 2 * 2                           // R | D tiles (3), stock tiles (2)
        + (size_t)((G + 15) & ~15) * 3 + 16                       // episode-end rows (3) + pad
@@ -168,8 +150,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   // The value tables are REPLICATED so that a lane's lookup lands in the lane's own LDS bank (ds_read_b32: 32 banks, lane
   // groups of 32): entry v of copy c at dword v * 32 + c, lane l reads copy l & 31 -- no bank conflicts whatever the values.
   float* s_tabs = (float*)smem;                                         // [101][32] stock / 100        encode_observation,
-  constexpr int NC = (GT == 48) ? SW_NC48 : 32, NCL = (NC == 32) ? 7 : 6;      // table copies; log2 of an entry's bytes
-  static_assert(NC == 32 || NC == 16, "SW_NC48: 32 or 16");
+  constexpr int NC = 32, NCL = 7;                                       // table copies; log2 of an entry's bytes
   float* s_tabn = s_tabs + 101 * NC;                                    // [32][32]  x / norm           supply_chain.py:124-134
   // compute_reward (:147): f32(f64 sales - 0.1 * stock) depends on n = 10 * sales - stock only and equals the f32 quotient n / 10
   // for every reachable (sales <= 30, stock <= 100) (tests/test_host_logic.py); 8 copies: lanes l, l + 8, .. share one
@@ -199,18 +180,6 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   auto div_PF = [&](uint32_t i) { return GT ? i / (uint32_t)(GT ? GT / 16 : 1) : (a.mPF ? __umulhi(i, a.mPF) : i); };
   const int n_store_waves = GT ? NSTORE : a.n_store_waves;
   const int rec_threads = (GT ? NREC : a.n_rec_waves) << 6, store_first = rec_threads, work_first = rec_threads + (n_store_waves << 6);
-#ifdef PHX_TIMING
-  unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-  unsigned long long rts[8]; rts[6] = rts[7] = 0; rts[0] = __builtin_amdgcn_s_memrealtime();
-#define RSTAMP(k) do { rts[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define RSTAMP(k) do {} while (0)
-#endif
-#if defined(PHX_TIMING) && !defined(PHX_RT_ONLY)     /* PHX_RT_ONLY: the wall-clock stamps alone (six per workgroup: no perturbation to speak of) */
-#define STICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tm[k] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define STICK(k) do {} while (0)
-#endif
 
   // ---- the workgroup's pair groups, one after the other (a launch of more groups than resident workgroups: replacing a finished
   //      1 024-thread, 160 KB workgroup by the next costs the CU 3-4 us -- tools/ubench/ub_anyorder.hip -- and the tables would be
@@ -272,11 +241,8 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
       const int wf = (__ballot(f0) != 0ull ? 1 : 0) | (__ballot(f1) != 0ull ? 2 : 0) | (__ballot(f2) != 0ull ? 4 : 0);
       if ((tid & 63) == 0 && tid < 256) s_flags[tid >> 6] = wf;
     }
-    STICK(6);
     __syncthreads();
-    STICK(7);
   }
-  STICK(0); RSTAMP(1);
   int launch_flags = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) if (k * 64 < NT) launch_flags |= s_flags[k];
@@ -313,11 +279,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   //      shop, env and tick come from registers set once per launch instead of two dependent LDS lookups per item (an LDS
   //      round trip is ~200 cycles in which the wave does nothing else: the draw phase had seven of them per item).
   const int nwk = NT - work_first, wt = tid - work_first;               // worker threads, this thread's rank among them
-#ifdef SW_NO_FIXED_DRAWS
-  const bool draws_fixed = false;
-#else
   const bool draws_fixed = (nwk % G) == 0;
-#endif
   int dl_gl = 0, dl_jr0 = 0, dl_s = 0, dl_pos0 = 0; uint32_t dl_tick0 = 0; int64_t dl_genv = 0;
   // FSM: q mod num_steps for q < 2^17 (the f32 quotient is off by one at most)
   const uint32_t ns_u = (uint32_t)a.num_steps; const float inv_ns_f = 1.0f / (float)a.num_steps;
@@ -389,11 +351,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
       // FSM: the words of the four rows' episode positions ((position at launch + row) mod num_steps; tla >= -3): the lookups are in
       // flight while the Philox block is computed
       uint32_t pw[4] = {0u, 0u, 0u, 0u};
-#ifndef SWF_ABL_NOPW
       if (FSM)
-#else
-      if (false)
-#endif
       {
         uint32_t pos;
         if (fixed) { int p = pos0 + tla; if (p < 0) p += (int)ns_u; else if (p >= (int)ns_u) p -= (int)ns_u; pos = (uint32_t)p; }     // (-3 <= tla < tc <= num_steps)
@@ -404,11 +362,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
       uint32_t w[4] = {0u, 0u, 0u, 0u};
       uint32_t y[4] = {0u, 0u, 0u, 0u}, aj[4] = {0u, 0u, 0u, 0u};
       if (!(rp_act && rp_exo)) {
-#ifdef PHX_ABL_NODRAW
-      w[0] = tick_a * 2654435761u + (uint32_t)genv; w[1] = w[0] * 40503u + s; w[2] = w[1] ^ 0x9e3779b9u; w[3] = w[2] + w[0];   // dev ablation: no Philox
-#else
       rng_block(a.seed, genv, tick_a, s, 0, 0, w);
-#endif
       bool rej = false;
 #pragma unroll
       for (int h = 0; h < 4; ++h) rej |= !rng_split(w[h], y[h], aj[h]);
@@ -426,11 +380,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
       for (int h = 0; h < 4; ++h) {
         uint32_t yy = y[h];
         if (!k6) yy -= __umul24((uint32_t)((float)yy * a.inv_pK), a.pK);  // the first K base-5 digits: y mod 5^K
-#ifdef SW_ABL_NODTAB     /* attribution of the LDS bank conflicts: the order sum by arithmetic instead of the byte gather (same value) */
-        D[h] = rp_exo ? Dx[h] : rng_digit_sum(yy, a.K, nullptr);
-#else
         D[h] = rp_exo ? Dx[h] : (int)s_dtab[yy];                         // the customers' order sizes summed, supply_chain.py:61-67
-#endif
       }
       const int i = __mul24(tla, G) + gl;
 #pragma unroll
@@ -440,11 +390,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
         // decode_action: int(round(action)), supply_chain.py:139.  A replayed action >= -0.5 (the call's pre-scan) rounds to R >= 0 and
         // min(R, 100 - stock) is the same for every R >= 100: 255 stands for all of them in the tile's byte
         const int Rq = rp_act ? (int)fminf(rintf(action), 255.0f) : (int)rintf(action);
-#ifdef SWF_ABL_NOPW
-        if (false)
-#else
         if (FSM)        // the stage's masks folded into the operands (no action: no request; no orders: no demand), its flags beside them
-#endif
           s_rd[i + h * G] = (uint16_t)((((uint32_t)Rq | ((uint32_t)D[h] << 8)) | SWF_FLAGS) & pw[h]);
         else
         s_rd[i + h * G] = (uint16_t)(Rq | (D[h] << 8));
@@ -570,11 +516,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   // the tables; written to LDS in the layout of the trajectory rows (the store waves copy whole rows of pieces).  Where
   // the worker threads are a multiple of G / 4, a lane keeps its column for the whole launch (no division per unit).
   const int G4 = G >> 2;
-#ifdef SW_NO_FIXED_OUT
-  const bool out_fixed = false;
-#else
   const bool out_fixed = (nwk % G4) == 0;
-#endif
   const int ol_r0 = wt >= 0 ? (int)div_G4((uint32_t)wt) : 0, ol_gl0 = wt >= 0 ? (wt - ol_r0 * G4) << 2 : 0;
   auto outputs = [&](int c, int tc) __attribute__((always_inline)) {
     if (wt < 0) return;
@@ -624,11 +566,7 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
           o[3 * k] = *(const float*)(t_s + as_[k]);                     // encode_observation :124-134
           o[3 * k + 1] = *(const float*)(t_n + an_[k]);
           o[3 * k + 2] = *(const float*)(t_n + am_[k]);
-#ifdef SW_ABL_NORTAB     /* attribution: the reward as the f32 quotient (the same value, tests/test_host_logic.py) instead of the 8-copy table */
-          rw[k] = (float)((int)(ar_[k] >> 5) - 100) / 10.0f;
-#else
           rw[k] = *(const float*)(t_r + ar_[k]);                        // compute_reward :147, rounded once to f32
-#endif
         }
         if (FSM && __builtin_expect(((fo4[0] | fo4[1] | fo4[2] | fo4[3]) & SWF_FO_LAUNCH) != 0u, 0)) {      // rows before the fragment's first rewarded step
 #pragma unroll
@@ -663,14 +601,10 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   //      can overlap -- tile reads of chunk co are in flight while the block of chunk cd is computed, the sixteen table lookups while
   //      its words are split, the four order-sum lookups while the staged tile is written.  (Separately the output phase is ~100
   //      instructions around two exposed LDS round trips, ~20 cycles per instruction.)  The one-in-3e5 rejected word is repaired after the fact.
-#ifdef SW_NO_FUSED_WORK
-  const bool fused_ok = false;
-#else
   // (the FSM instantiation, already at 127 VGPRs, loses with it: config 3, T = 400 894 against 850 us)
   // (replays: of the actions only -- 64.7 against 67.0 us per T = 400; with the order sizes too the fused form loses, 85.9 against 83.7)
   const bool fused_mode = MODE == 0 || (MODE == 1 && !rp_exo);
   const bool fused_ok = fused_mode && GT > 0 && TC == 16 && draws_fixed && out_fixed && !quad_extra && nwk == TC * G4 && nwk == (TC / 4) * G;
-#endif
   auto work_fused = [&](int co, int cd, int t0d) __attribute__((always_inline)) {
     if (wt < 0) return;
     // (1) outputs: the unit's tile words
@@ -796,11 +730,8 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
     //  the stores' pace is the memory system's, not the LDS round trips'; bursts make it worse.)
         // (ONE piece per trip since late round 5: the stores of a lane then leave evenly over the iteration instead of in bursts of four --
     //  the 8-fragment bench shape 111.5-112.3 against 113.6-118.4 us per call on a slow box, 108.6 against 112.1-113.7 on another, the
-    //  bench line +4 %; every other shape within noise.  SW_STORE_DEPTH: development.)
-#ifndef SW_STORE_DEPTH
-#define SW_STORE_DEPTH 1
-#endif
-    constexpr int SW_DEPTH = SW_STORE_DEPTH;
+    //  bench line +4 %; every other shape within noise.)
+    constexpr int SW_DEPTH = 1;
     for (; q + (uint32_t)(SW_DEPTH - 1) * dq < n; q += (uint32_t)SW_DEPTH * dq, sp += (uint32_t)SW_DEPTH * dq) {
       float4 v[SW_DEPTH];
 #pragma unroll
@@ -808,15 +739,11 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
       uint32_t o[SW_DEPTH];
 #pragma unroll
       for (int k = 0; k < SW_DEPTH; ++k) { o[k] = off; pc += dp; off += d_off; if (pc >= P) { pc -= P; off += wrap; } }
-#ifndef PHX_ABL_NOSTORE
 #pragma unroll
       for (int k = 0; k < SW_DEPTH; ++k) sw_store16(dst + (size_t)o[k], v[k]);
-#endif
     }
     for (; q < n; q += dq, sp += dq) {
-#ifndef PHX_ABL_NOSTORE
       sw_store16(dst + (size_t)off, sp[0]);
-#endif
       pc += dp; off += d_off;
       if (pc >= P) { pc -= P; off += wrap; }
     }
@@ -859,7 +786,6 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   // (agents.py:292-323).  So the workgroup's G-byte segments of all T rows are written BEFORE the first chunk is streamed instead of
   // with every chunk: on some boxes the two planes cost the steady state 8-10 us per launch (tools/ubench/ub_store10.hip, FLAGS 0 / 1).
   auto flag_segments = [&](int part) __attribute__((always_inline)) {
-#ifndef PHX_ABL_NOSTORE
     const uint32_t uT = (uint32_t)a.T, ns = (uint32_t)a.num_steps, PF = (uint32_t)(G >> 4);
     const uint32_t p_lo = part == 0 ? 0u : (part == 1 ? (uT * 2u) / 5u : (uT * 13u) / 20u), p_hi = part == 0 ? (uT * 2u) / 5u : (part == 1 ? (uT * 13u) / 20u : uT);
     const float inv_ns = 1.0f / (float)ns;
@@ -925,13 +851,10 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
             }
             vo = make_uint4(wo[0], wo[1], wo[2], wo[3]); vr = make_uint4(wr[0], wr[1], wr[2], wr[3]);
           }
-#ifndef SWF_ABL_NOFLAGS
           put(p_ov + off, vo); put(p_rv + off, vr);
-#endif
         }
       }
     }
-#endif
   };
 
   // ---- state after the fragment: written by the recurrence lanes as soon as the last chunk's chain is done (iteration n_chunks - 1,
@@ -1013,69 +936,31 @@ __global__ __launch_bounds__(1024) void phx_sc_rollout_sw_kernel(const SwArgs a_
   //        workers: outputs(it), draws(it + 2) | recurrence lanes: recurrence(it + 1) | store waves: stores(it - 1), actions(it + 1)    one barrier
   for (int it = -2; it <= n_chunks; ++it) {
     SW_REFRESH();
-#ifdef PHX_RT_FILL
-#define RSTAMP_WORK() do { if (it >= -2 && it <= 2) RSTAMP(it + 4); } while (0)      /* slots 2..6: own work of iterations -2..2 done (before the barrier) */
-    if (it == 3) RSTAMP(7);
-#else
-#define RSTAMP_WORK() do {} while (0)
-    if (it == 1) RSTAMP(2);
-    if (it == -1) RSTAMP(6);
-    if (it == 0) RSTAMP(7);
-    if (it == n_chunks) RSTAMP(3);
-#endif
     const int co = it, cr = it + 1, cd = it + 2, cs = it - 1;
     if (tid >= work_first) {
       // workers (letting every other worker wave draw first, so that LDS-heavy and VALU-heavy phases overlap on a SIMD, changes nothing)
       if (fused_ok && co >= 0 && cd < n_chunks && rows_of(co) == TC && rows_of(cd) == TC && !(weird && co == 0)) {
         work_fused(co, cd, start_of(cd));
-        STICK(2);
       } else {
       if (co >= 0 && co < n_chunks) outputs(co, rows_of(co));
-      STICK(2);
       if (cd < n_chunks) draws(start_of(cd), rows_of(cd), cd);
-      STICK(1);
       }
     } else if (tid < rec_threads) {
-#ifdef SWF_ABL_PLAINREC
-      if (cr >= 0 && cr < n_chunks) recurrence(cr, rows_of(cr));
-#else
       if (cr >= 0 && cr < n_chunks) { if (FSM) recurrence_fsm(cr, rows_of(cr)); else recurrence(cr, rows_of(cr)); }
-#endif
       else if (it == -2 && pass == 0) replicate_tables(tid, work_first);
       else if (cr == n_chunks) finish();
-      STICK(3);
     } else {
       if (it == -2 && pass == 0) replicate_tables(tid, work_first);
-#ifndef SW_STORE_PRIO
-#define SW_STORE_PRIO 2
-#endif
-      __builtin_amdgcn_s_setprio(SW_STORE_PRIO);      // the store lanes' single-piece trips are paced by their LDS round trips: issue them ahead of the workers (-1 % on the bench shape)
+      __builtin_amdgcn_s_setprio(2);      // the store lanes' single-piece trips are paced by their LDS round trips: issue them ahead of the workers (-1 % on the bench shape)
       if (REPLAY) touch_inputs(it + 3);
       if (it <= 0) flag_segments(it + 2);
       if (cs >= 0) stores(cs, start_of(cs), rows_of(cs));
       if (cr >= 0 && cr < n_chunks) store_actions(cr, start_of(cr), rows_of(cr));     // (drawn in the previous iteration)
-      STICK(4);
     }
-    RSTAMP_WORK();
-    sw_lds_barrier(); STICK(5);
+    phx_lds_barrier();
   }
   if (REPLAY && pf_acc == 0x5EEDF00Du && a.T < 0) a.env_arrive[0] = (int32_t)pf_acc;     // (never true: keeps the touches alive)
   }   // pair groups of the workgroup
-#ifndef PHX_RT_FILL
-  RSTAMP(4);
-#endif
-#ifdef PHX_TIMING
-  if (a.timing && (tid & 63) == 0) for (int q = 0; q < 8; ++q) a.timing[((int64_t)blockIdx.x * 16 + (tid >> 6)) * 8 + q] = tm[q];
-#endif
-#ifdef PHX_TIMING
-#ifdef PHX_RT_FILL
-  { const int role = tid == 0 ? 0 : (tid == store_first ? 1 : (tid == work_first ? 2 : -1));
-    if (a.rt && role >= 0) for (int q = 0; q < 8; ++q) a.rt[((int64_t)(a.launch_idx & 3) * 8192 + blockIdx.x * 3 + role) * 8 + q] = rts[q]; }
-#else
-  RSTAMP(5);
-  if (a.rt && tid == 0) for (int q = 0; q < 8; ++q) a.rt[((int64_t)(a.launch_idx & 3) * 8192 + blockIdx.x) * 8 + q] = rts[q];
-#endif
-#endif
 }
 
 #undef a
@@ -1101,7 +986,6 @@ void phx_sc_sw_tables(int K, int norm, std::vector<uint8_t>* out) {
   for (int e = 0; e < n5; ++e) { int v = e, sum = 0; while (v) { sum += v % 5; v /= 5; } dtab[e] = (uint8_t)sum; }
 }
 
-static uint32_t sw_magic32(int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)(d > 0 ? d : 1)); }
 static const size_t SW_LDS_MAX = 160 * 1024;
 
 // Decides whether an env shape takes the store-wave kernel and with which workgroup shape.  `block`: phx_spec.variant_block
@@ -1113,16 +997,12 @@ bool phx_sc_sw_plan(int B, int S, int K_uniform, bool norm_uniform, int num_step
   const int64_t total = (int64_t)B * S;
   if (total >= ((int64_t)1 << 24)) return false;                                  // 24-bit multiplies on (row, pair) offsets
   int dtab_n = 1; for (int k = 0; k < K_uniform; ++k) dtab_n *= 5;
-  const int tc_env = phx_knobs().sw_tc;            // development default
-  const int ns_env = phx_knobs().sw_store_waves;
-  const int nw_env = phx_knobs().sw_work_waves;
   auto epb_of = [&](int G) { return (G + S - 2) / S + 1; };                        // the most envs a block can touch
   auto pairs_ok = [&](int G) { return G >= 16 && G <= 256 && G % 16 == 0 && total % G == 0 && epb_of(G) <= 255; };
   auto tc_ok = [&](int G, int tc) {
     return tc <= num_steps && (int64_t)tc * total * 12 < ((int64_t)1 << 32) && sw_lds_bytes(G, epb_of(G), tc, dtab_n, fsm_ns) <= SW_LDS_MAX;
   };
   auto tc_for = [&](int G) {
-    if (tc_env == 16 || tc_env == 20) return tc_ok(G, tc_env) ? tc_env : 0;
     if ((G == 144 || G == 128 || G == 96 || G == 48) && tc_ok(G, 16)) return 16;              // the shapes with a compile-time instantiation (16-row chunks)
     return tc_ok(G, 20) ? 20 : (tc_ok(G, 16) ? 16 : 0);
   };
@@ -1146,8 +1026,8 @@ bool phx_sc_sw_plan(int B, int S, int K_uniform, bool norm_uniform, int num_step
   if (!G) return false;
   p->G = G; p->epb = epb_of(G); p->K = K_uniform; p->tc = tc_for(G); p->dtab_n = dtab_n;
   p->n_rec = (G + 63) / 64;
-  p->n_store = ns_env > 0 ? ns_env : (G >= 96 ? 4 : (G >= 48 ? 2 : 1));
-  int work = nw_env > 0 ? nw_env : (p->tc * (G / 4) + 63) / 64;
+  p->n_store = G >= 96 ? 4 : (G >= 48 ? 2 : 1);
+  int work = (p->tc * (G / 4) + 63) / 64;
   if (work < 1) work = 1;
   if (p->n_rec + p->n_store + work > 16) work = 16 - p->n_rec - p->n_store;
   p->nt = 64 * (p->n_rec + p->n_store + work);
@@ -1194,12 +1074,10 @@ hipError_t phx_launch_sc_rollout_sw(const DevSpec& sp, const phx_rollout_io& io,
   const bool replay = io.actions != nullptr || io.exo != nullptr;
   SwArgs a; memset(&a, 0, sizeof a);
   a.B = sp.B; a.S = sp.S; a.epb = p.epb; a.G = p.G; a.K = p.K; a.T = io.T; a.num_steps = sp.num_steps;
-  const int remap_env = phx_knobs().rollout_remap;
-  a.xcd_remap = remap_env >= 0 ? remap_env : 1;
+  a.xcd_remap = 1;
   a.n_rec_waves = p.n_rec; a.n_store_waves = p.n_store; a.dtab_n = p.dtab_n;
-  static const float inv[7] = {1.0f, 0.2f, 0.04f, 0.008f, 0.0016f, 0.00032f, 0.000064f};
-  a.pK = (uint32_t)p.dtab_n; a.inv_pK = inv[p.K];
-  a.mG = sw_magic32(p.G); a.mG4 = sw_magic32(p.G / 4); a.mS = sw_magic32(sp.S); a.mPO = sw_magic32(3 * (p.G / 4)); a.mPF = p.G / 16 > 1 ? sw_magic32(p.G / 16) : 0;     // (the magic of 1 does not fit 32 bits: 0 = no division)
+  a.pK = (uint32_t)p.dtab_n; a.inv_pK = inv_pow5[p.K];
+  a.mG = phx_magic32(p.G); a.mG4 = phx_magic32(p.G / 4); a.mS = phx_magic32(sp.S); a.mPO = phx_magic32(3 * (p.G / 4)); a.mPF = p.G / 16 > 1 ? phx_magic32(p.G / 16) : 0;     // (the magic of 1 does not fit 32 bits: 0 = no division)
   a.norm = p.norm; a.seed = sp.seed; a.env_offset = sp.env_offset;
   a.first_rows = io.T <= p.tc ? io.T : p.tc;
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES];
@@ -1238,37 +1116,10 @@ hipError_t phx_launch_sc_rollout_sw(const DevSpec& sp, const phx_rollout_io& io,
   // the grid: one workgroup per pair group up to what the chip holds at once, the rest of the groups are walked by the same workgroups
   a.n_groups = (int32_t)(((int64_t)sp.B * sp.S) / p.G);
   unsigned n_wg = (unsigned)a.n_groups;
-  if (phx_knobs().sw_persist) {
-    const int n_cu = phx_device_cu_count();
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(SW_LDS_MAX / (size_t)p.lds, (size_t)(2048 / p.nt)));
-    unsigned resident = (unsigned)n_cu * per_cu;
-    if (n_wg > resident) n_wg = resident >= 8 ? resident & ~7u : resident;        // (a multiple of 8: virtual workgroup vb stays on the XCD of vb % 8)
-  }
+  const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(SW_LDS_MAX / (size_t)p.lds, (size_t)(2048 / p.nt)));
+  const unsigned resident = (unsigned)phx_device_cu_count() * per_cu;
+  if (n_wg > resident) n_wg = resident >= 8 ? resident & ~7u : resident;          // (a multiple of 8: virtual workgroup vb stays on the XCD of vb % 8)
   const dim3 grid(n_wg);
-#ifdef PHX_TIMING
-  { static unsigned long long* tbuf = nullptr; if (!tbuf) { (void)hipMalloc((void**)&tbuf, 8 * 16 * 8192 * sizeof(unsigned long long)); (void)hipMemset(tbuf, 0, 8 * 16 * 8192 * sizeof(unsigned long long)); } a.timing = grid.x <= 8192 ? tbuf : nullptr;
-    { static unsigned long long* rbuf = nullptr; static int li = 0; if (!rbuf) (void)hipMalloc((void**)&rbuf, (4 * 8192 * 8) * sizeof(unsigned long long)); a.rt = grid.x <= 8192 ? rbuf : nullptr; a.launch_idx = li++;
-      if (getenv("PHX_TIMING_DUMP") && li == 44) { (void)hipDeviceSynchronize(); std::vector<unsigned long long> h(4 * 8192 * 8); (void)hipMemcpy(h.data(), rbuf, h.size() * 8, hipMemcpyDeviceToHost);
-#ifdef PHX_RT_FILL
-        { const char* rn[3] = {"rec", "store", "work"}; const char* nm2[8] = {"entry", "setup done", "it -2 work done", "it -1 work done", "it 0 work done", "it 1 work done", "it 2 work done", "it 3 starts"};
-          for (int r = 0; r < 3; ++r) for (int q = 1; q < 8; ++q) { double sum = 0, mx = 0; for (unsigned b = 0; b < grid.x; ++b) { const unsigned long long* e = &h[((size_t)1 * 8192 + b * 3 + r) * 8]; const double v = (double)(long long)(e[q] - e[0]) * 0.01; sum += v; mx = std::max(mx, v); }
-            fprintf(stderr, "SW_RTF launch 41 %-5s %-18s mean %7.2f max %7.2f us after the workgroup's entry\n", rn[r], nm2[q], sum / grid.x, mx); } }
-#endif
-        // launches 40..42 (slots 0..2): stamps in 10 ns ticks relative to the earliest entry of launch 40
-        unsigned long long base = ~0ull; for (unsigned b = 0; b < grid.x; ++b) base = std::min(base, h[((size_t)0 * 8192 + b) * 8]);
-        const char* nm[8] = {"entry", "setup done", "it 1 (first stores)", "it n_chunks (drain)", "loop done", "end", "it -1", "it 0"};
-        for (int l = 0; l < 3; ++l) for (int q : {0, 1, 6, 7, 2, 3, 4, 5}) { double mn = 1e30, mx = -1e30, sum = 0; for (unsigned b = 0; b < grid.x; ++b) { const double v = (double)(long long)(h[((size_t)l * 8192 + b) * 8 + q] - base) * 0.01; mn = std::min(mn, v); mx = std::max(mx, v); sum += v; }
-          fprintf(stderr, "SW_RT launch %d  %-22s min %8.2f  mean %8.2f  max %8.2f us\n", 40 + l, nm[q], mn, sum / grid.x, mx); }
-        // launch 41 by XCD (workgroup b runs on XCD b % 8): entry and end, relative to the launch's earliest entry
-        { unsigned long long b1 = ~0ull; for (unsigned b = 0; b < grid.x; ++b) b1 = std::min(b1, h[((size_t)1 * 8192 + b) * 8]);
-          for (int xc = 0; xc < 8; ++xc) { double se = 0, sx = 0, mxx = 0, mnx = 1e30; int n = 0; for (unsigned b = xc; b < grid.x; b += 8) { const unsigned long long* e = &h[((size_t)1 * 8192 + b) * 8]; const double en = (double)(long long)(e[0] - b1) * 0.01, ex = (double)(long long)(e[5] - b1) * 0.01; se += en; sx += ex; mxx = std::max(mxx, ex); mnx = std::min(mnx, ex); ++n; }
-            fprintf(stderr, "SW_RT launch 41 XCD %d: entry mean %6.2f | end min %6.2f mean %6.2f max %6.2f us\n", xc, se / n, mnx, sx / n, mxx); } } } }
-    if (getenv("PHX_TIMING_DUMP")) { static int calls = 0; if (++calls == 20 && a.timing) { (void)hipDeviceSynchronize(); std::vector<unsigned long long> h(8 * 16 * 8192); (void)hipMemcpy(h.data(), tbuf, h.size() * 8, hipMemcpyDeviceToHost);
-      const char* role[3] = {"rec  ", "store", "work "}; const int nwv = p.nt / 64;
-      for (int r = 0; r < 3; ++r) { double sum[8] = {0}; int n = 0;
-        for (unsigned b = 0; b < grid.x; ++b) for (int w = 0; w < nwv; ++w) { const int rr = w < p.n_rec ? 0 : (w < p.n_rec + p.n_store ? 1 : 2); if (rr != r) continue; ++n; for (int q = 0; q < 8; ++q) sum[q] += (double)h[((size_t)b * 16 + w) * 8 + q]; }
-        fprintf(stderr, "SW_TIMING %s waves (%d): setup %.0f (before 1st barrier %.0f, in it %.0f) | draws %.0f | outputs %.0f | rec %.0f | stores %.0f | barrier %.0f   cycles per wave and launch\n", role[r], n, sum[0]/n, sum[6]/n, sum[7]/n, sum[1]/n, sum[2]/n, sum[3]/n, sum[4]/n, sum[5]/n); } } } }
-#endif
   phx_note_kernel(fsm ? "phx_sc_rollout_sw_kernel[fsm]" : (replay ? "phx_sc_rollout_sw_kernel[replay]" : "phx_sc_rollout_sw_kernel"));
   // more than 64 KB of dynamic LDS needs the attribute (once per instantiation and device)
 #define SW_LAUNCH_(TC_, GT_, NREC_, NSTORE_, NWORK_, RP_) do { \
@@ -1277,16 +1128,15 @@ hipError_t phx_launch_sc_rollout_sw(const DevSpec& sp, const phx_rollout_io& io,
     hipLaunchKernelGGL((phx_sc_rollout_sw_kernel<TC_, GT_, NREC_, NSTORE_, NWORK_, RP_>), grid, dim3(p.nt), (size_t)p.lds, st, a); } while (0)
 #define SW_LAUNCH_PLAIN(TC_, GT_, NREC_, NSTORE_, NWORK_) do { if (replay) SW_LAUNCH_(TC_, GT_, NREC_, NSTORE_, NWORK_, 1); else SW_LAUNCH_(TC_, GT_, NREC_, NSTORE_, NWORK_, 0); } while (0)
 #define SW_LAUNCH(TC_, GT_, NREC_, NSTORE_, NWORK_) do { if (fsm) SW_LAUNCH_(TC_, GT_, NREC_, NSTORE_, NWORK_, 2); else SW_LAUNCH_PLAIN(TC_, GT_, NREC_, NSTORE_, NWORK_); } while (0)
-  const int generic_env = phx_knobs().sw_generic;      // development: the run-time-shape instantiation
   const int work = p.nt / 64 - p.n_rec - p.n_store;
 #define SW_SHAPE(G_, NREC_, NSTORE_, NWORK_) (p.tc == 16 && p.G == G_ && p.n_rec == NREC_ && p.n_store == NSTORE_ && work == NWORK_)
   // (144-pair workgroups: no FSM instantiation -- its sections do not fit beside 16-row tiles of 144 pairs)
-  if (!generic_env && !fsm && SW_SHAPE(144, 3, 4, 9)) SW_LAUNCH_PLAIN(16, 144, 3, 4, 9);
-  else if (!generic_env && !fsm && SW_SHAPE(144, 3, 2, 9)) SW_LAUNCH_PLAIN(16, 144, 3, 2, 9);
-  else if (!generic_env && SW_SHAPE(128, 2, 4, 8)) SW_LAUNCH(16, 128, 2, 4, 8);
-  else if (!generic_env && SW_SHAPE(96, 2, 4, 6)) SW_LAUNCH(16, 96, 2, 4, 6);
-  else if (!generic_env && SW_SHAPE(96, 2, 2, 6)) SW_LAUNCH(16, 96, 2, 2, 6);
-  else if (!generic_env && SW_SHAPE(48, 1, 2, 3)) SW_LAUNCH(16, 48, 1, 2, 3);
+  if (!fsm && SW_SHAPE(144, 3, 4, 9)) SW_LAUNCH_PLAIN(16, 144, 3, 4, 9);
+  else if (!fsm && SW_SHAPE(144, 3, 2, 9)) SW_LAUNCH_PLAIN(16, 144, 3, 2, 9);
+  else if (SW_SHAPE(128, 2, 4, 8)) SW_LAUNCH(16, 128, 2, 4, 8);
+  else if (SW_SHAPE(96, 2, 4, 6)) SW_LAUNCH(16, 96, 2, 4, 6);
+  else if (SW_SHAPE(96, 2, 2, 6)) SW_LAUNCH(16, 96, 2, 2, 6);
+  else if (SW_SHAPE(48, 1, 2, 3)) SW_LAUNCH(16, 48, 1, 2, 3);
   else if (p.tc == 20) SW_LAUNCH(20, 0, 0, 0, 0);
   else SW_LAUNCH(16, 0, 0, 0, 0);
 #undef SW_SHAPE

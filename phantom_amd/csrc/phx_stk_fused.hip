@@ -17,24 +17,14 @@
 
 #define STK_NT 256
 #define STKR_SLOTS 3
-#ifndef STKR_W384
-#define STKR_W384 6
-#endif
-#define STKR_MINWAVES(NT) ((NT) == 384 ? STKR_W384 : ((NT) / 64 < 4 ? 4 : ((NT) / 64 > 8 ? 8 : (NT) / 64)))
+#define STKR_MINWAVES(NT) ((NT) / 64 < 4 ? 4 : ((NT) / 64 > 8 ? 8 : (NT) / 64))
 __host__ __device__ inline size_t g_stk_paid_off(int nSell) { return ((size_t)nSell * (8 + 8 + 8 + 4 + 4 + 1) + 15) & ~(size_t)15; }
-#ifdef PHX_TIMING
-__device__ unsigned long long g_stk_tm[8];
-__device__ unsigned long long g_stk_rt[8];      // wall clock (100 MHz) of the last rollout launch: [0] min entry, [1] max exit, [2..4] sums of setup / loop / epilogue, [5] blocks, [6] sum of (entry - min entry)
-#define STICK(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); stm[k] += now_ - sprev; sprev = now_; } while (0)
-#else
-#define STICK(k) do {} while (0)
-#endif
 
 // SellerAgent.handle_order, n times in one round (stackelberg test agents: self.revenue += self.price * vol, one Order(1) per buying
 // neighbour): the sequential f64 sum of n EQUAL addends.  From a revenue of +0 (the followers' step resets it before the round) and for an
 // addend that is a float32 value (the price is the seller's f32 action) every partial sum k * amount has at most 24 + 11 significant bits:
 // each addition is exact, and so is ONE multiplication -- the popular sellers of a 128 x 1024 market book ~100 orders, and the whole
-// workgroup waits at the barrier behind that chain (PHX_TIMING: 1.8 k of a step's 8.7 k cycles).  Anything else keeps the loop.
+// workgroup waits at the barrier behind that chain (cycle counters: 1.8 k of a step's 8.7 k cycles).  Anything else keeps the loop.
 __device__ __forceinline__ double stk_book(double rev, double amount, int n) {
   const bool exact = __double_as_longlong(rev) == 0ll && amount != 0.0 && (double)(float)amount == amount && n <= 2048;
   if (exact) return __dmul_rn((double)n, amount);
@@ -91,11 +81,7 @@ __global__ __launch_bounds__(STK_NT) void phx_stk_step_kernel(const DevSpec sp, 
     s_count[k] = 0; s_sent[k] = 0;
   }
   for (int k = tid; k < nBuy; k += STK_NT) s_bought[k] = 0xFF;
-#ifdef PHX_TIMING
-  unsigned long long stm[8] = {0}, sprev = __builtin_readcyclecounter();
-#endif
   __syncthreads();
-  STICK(0);
 
   // ---- acting phase (_handle_acting_agents, env.py:320-336): decode_action of every acting agent.
   //      Sellers only record the new price (the Price messages land after the acting phase:
@@ -133,9 +119,7 @@ __global__ __launch_bounds__(STK_NT) void phx_stk_step_kernel(const DevSpec sp, 
       s_bought[kr] = (uint8_t)bought; s_paid[kr] = paid;                     // read back by compute_reward below
     }
   }
-  STICK(1);
   __syncthreads();
-  STICK(2);
   // ---- pre_message_resolution + the single round: sellers book their orders (one add per Order,
   //      in inbox order: all addends are the same f64); this step's Price messages land in every
   //      neighbour's slot, i.e. the seller's posted price changes -----------------------------------
@@ -153,9 +137,7 @@ __global__ __launch_bounds__(STK_NT) void phx_stk_step_kernel(const DevSpec sp, 
     fld<int32_t>(sp, F_SELLER_TX)[sbase + kr] = tx;
     if (s_sent[kr]) { fld<double>(sp, F_SELLER_PRICE)[sbase + kr] = s_price[kr]; s_posted[kr] = s_price[kr]; posted_b[kr] = s_price[kr]; }
   }
-  STICK(3);
   __syncthreads();
-  STICK(4);
   // ---- obs / reward / done in ONE pass (stackelberg.py:142-196).  Neither kind terminates or
   //      truncates (agents.py:292-323), so "terminal" is the step count alone (env.py:312-318).
   const bool terminal = (t == sp.num_steps);
@@ -210,18 +192,14 @@ __global__ __launch_bounds__(STK_NT) void phx_stk_step_kernel(const DevSpec sp, 
     io.obs_valid[o] = ov; io.reward_valid[o] = rv; io.done_valid[o] = 1;
     io.terminated[o] = 0; io.truncated[o] = 0;
   }
-  STICK(5);
   if (tid == 0) {
     fld<int32_t>(sp, F_ENV_STEP)[b] = t;
     fld<int32_t>(sp, F_ENV_TICK)[b] = (int32_t)(tick + 1);
     io.all_terminated[b] = 0; io.all_truncated[b] = terminal;
   }
-#ifdef PHX_TIMING
-  if (blockIdx.x < 64 && (tid & 63) == 0 && (tid >> 6) == 1) for (int q = 0; q < 8; ++q) atomicAdd(&g_stk_tm[q], stm[q]);
-#endif
 }
 
-// ---- the same step, loads batched.  Measured on the kernel above (PHX_TIMING, 128 x 1024, B = 4096): 34 k cycles per
+// ---- the same step, loads batched.  Measured on the kernel above (cycle counters, 128 x 1024, B = 4096): 34 k cycles per
 // block, 13 k in the acting pass and 19 k in the output pass -- per agent three to four DEPENDENT table lookups (flags ->
 // record -> neighbour slots -> action / cache), 4.5 agents per lane one after the other; removing the output stores
 // (half of the kernel's bytes) saved 9 of 57 us.  Here a lane owns (up to) STKR_SLOTS agents, a = tid + k * NT, and the
@@ -230,11 +208,6 @@ __global__ __launch_bounds__(STK_NT) void phx_stk_step_kernel(const DevSpec sp, 
 // the agents that act and the reward cache of those that emit it without recomputing it.  Barriers order LDS only, so
 // batch (2) and the state stores stay in flight across them.  Static graphs with <= 8 neighbours per buyer
 // (DevSpec::stk_packed); the kernel above takes the rest.
-__device__ __forceinline__ void stk_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_step_fast_kernel(const DevSpec sp, const phx_step_io io) {
@@ -288,7 +261,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_step_fast_kerne
       if (!(fl & 4u) && (terminal || (fl & 2u))) { cv[k] = rew_cache_v[a]; cache[k] = rew_cache[a]; }
     }
   }
-  stk_lds_barrier();
+  phx_lds_barrier();
 
   auto cheapest = [&](int k, int deg, int& jr) __attribute__((always_inline)) {   // first minimum in neighbour order
     const uint32_t w[4] = {ag[k].x, ag[k].y, ag[k].z, ag[k].w};
@@ -321,7 +294,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_step_fast_kerne
       s_bought[kr] = (uint8_t)bought; s_paid[kr] = paid;
     }
   }
-  stk_lds_barrier();
+  phx_lds_barrier();
   // ---- pre_message_resolution + the single round ------------------------------------------------------------------
   for (int kr = tid; kr < nSell; kr += NT) {
     double rev = s_rev[kr]; int tx = s_tx[kr];
@@ -337,7 +310,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_step_fast_kerne
     fld<int32_t>(sp, F_SELLER_TX)[sbase + kr] = tx;
     if (s_sent[kr]) { fld<double>(sp, F_SELLER_PRICE)[sbase + kr] = s_price[kr]; s_posted[kr] = s_price[kr]; posted_b[kr] = s_price[kr]; }
   }
-  stk_lds_barrier();
+  phx_lds_barrier();
   // ---- obs / reward / done in one pass (stackelberg.py:142-196) -----------------------------------------------------
   char* const p_obs = (char*)(io.obs + abase * 2);
   char* const p_rew = (char*)(io.reward + abase);
@@ -401,7 +374,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_step_fast_kerne
 // the slots are full (1 152 agents: 384 threads x 3): what is static per agent -- its record, both flag bytes, a
 // buyer's neighbour list (<= 8 seller ranks, packed u16) and value, a seller's degree -- is loaded into registers
 // once, and the agent's Philox block is kept for the four ticks it covers (an agent acts on two of them).  Measured
-// before (PHX_TIMING, 512 threads, everything looked up per step): 15.3 k cycles per step = acting 6.3 k (Philox per
+// before (cycle counters, 512 threads, everything looked up per step): 15.3 k cycles per step = acting 6.3 k (Philox per
 // acting agent and step) + booking 1.8 k + outputs 7.0 k (four dependent table loads per agent), a quarter of the
 // lanes idle in the third pass over the agents.
 //
@@ -422,9 +395,6 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
 #define io (*(const phx_rollout_io*)(kp + 8))
 #define STKR_REFRESH() asm volatile("" : "+s"(spc), "+s"(kp))
   STKR_REFRESH();
-#ifdef PHX_TIMING
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int A = sp.A, B = sp.B;
@@ -541,10 +511,6 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
   __syncthreads();
   const bool pf_rank = FAST && __syncthreads_or(my_pf_bad) != 0;      // (uniform; for the whole launch)
   if (pf_rank) { rerank(); __syncthreads(); }
-#ifdef PHX_TIMING
-  unsigned long long stm[8] = {0}, sprev = __builtin_readcyclecounter();
-  const unsigned long long rt_loop = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // a buyer's cheapest current neighbour: first minimum in neighbour order (price slots hold the sellers' posted
   // prices); jr < 0: no neighbour this episode
@@ -661,9 +627,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
       act[k] = action;
       __builtin_amdgcn_sched_barrier(0);
     }
-    STICK(0);
-    stk_lds_barrier();      // orders LDS only: the row's stores stay in flight
-    STICK(1);
+    phx_lds_barrier();      // orders LDS only: the row's stores stay in flight
     // ---- pre_message_resolution + the single round --------------------------------------------------
     for (int kr = tid; kr < nSell; kr += NT) {
       double rev = s_rev[kr]; int tx = s_tx[kr];
@@ -678,12 +642,11 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
       if (s_sent[kr]) { s_posted[kr] = s_price[kr]; if (FAST) s_postf[kr] = (float)s_price[kr]; }
       s_count[kr] = 0; s_sent[kr] = 0;
     }
-    stk_lds_barrier();      // orders LDS only: the row's stores stay in flight
+    phx_lds_barrier();      // orders LDS only: the row's stores stay in flight
     if ((tt & 1) ? sa_lead : sa_foll) {                                      // (uniform) the booking pass may have changed posted prices
       cj = 0xFEFEFEFEu;
-      if (FAST && pf_rank) { rerank(); stk_lds_barrier(); }
+      if (FAST && pf_rank) { rerank(); phx_lds_barrier(); }
     }
-    STICK(2);
     // ---- obs / reward / flags -> trajectory row (stackelberg.py:142-196) -----------------------------
     const bool terminal = (tt == sp.num_steps);
     const bool last = (t == io.T - 1);
@@ -748,9 +711,7 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
       __builtin_amdgcn_sched_barrier(0);
     }
     step = tt; ++tick;
-    STICK(3);
-    stk_lds_barrier();      // orders LDS only: the row's stores stay in flight
-    STICK(4);
+    phx_lds_barrier();      // orders LDS only: the row's stores stay in flight
     if (terminal) {                                                          // the caller's env.reset()
       for (int k = tid; k < nSell; k += NT) { s_posted[k] = 1.0; s_price[k] = 0.0; s_rev[k] = 0.0; s_tx[k] = 0; if (FAST) s_postf[k] = 1.0f; }
       for (int k = tid; k < nBuy; k += NT) { s_paid[k] = 0.0; s_bought[k] = 0; }
@@ -761,13 +722,9 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
         ++episode; ++n_resets;
       }
       step = 0;
-      stk_lds_barrier();      // orders LDS only: the row's stores stay in flight
+      phx_lds_barrier();      // orders LDS only: the row's stores stay in flight
     }
   }
-#ifdef PHX_TIMING
-  if (blockIdx.x < 64 && (tid & 63) == 0 && (tid >> 6) == 1) for (int q = 0; q < 8; ++q) atomicAdd(&g_stk_tm[q], stm[q]);
-  const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-#endif
   if (dyn && n_resets > 0) {
     for (int i = tid; i < sp.n_conn; i += NT) fld<uint8_t>(sp, F_NET_CONN_ON)[(int64_t)b * sp.n_conn + i] = s_conn[i];
     if (tid == 0) fld<int32_t>(sp, F_ENV_EPISODE)[b] = (int32_t)episode;
@@ -783,14 +740,6 @@ __global__ __launch_bounds__(NT, STKR_MINWAVES(NT)) void phx_stk_rollout_kernel(
     fld<double>(sp, F_ENV_REW_CACHE)[abase + a] = s_cache[a]; fld<uint8_t>(sp, F_ENV_REW_CACHE_VALID)[abase + a] = s_cv[a];
   }
   if (tid == 0) { fld<int32_t>(sp, F_ENV_STEP)[b] = step; fld<int32_t>(sp, F_ENV_TICK)[b] = (int32_t)tick; }
-#ifdef PHX_TIMING
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned long long rt_exit = __builtin_amdgcn_s_memrealtime();
-    atomicMin(&g_stk_rt[0], rt_entry); atomicMax(&g_stk_rt[1], rt_exit);
-    atomicAdd(&g_stk_rt[2], rt_loop - rt_entry); atomicAdd(&g_stk_rt[3], rt_end - rt_loop); atomicAdd(&g_stk_rt[4], rt_exit - rt_end); atomicAdd(&g_stk_rt[5], 1ull);
-  }
-#endif
 }
 #undef sp
 #undef io
@@ -803,22 +752,11 @@ size_t phx_stk_rollout_lds(const DevSpec& sp) {
 }
 
 hipError_t phx_launch_stk_rollout(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st) {
-#ifdef PHX_TIMING
-  { static int calls = 0; if (getenv("PHX_TIMING_DUMP") && ++calls == 10) { (void)hipDeviceSynchronize(); unsigned long long h[8];
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stk_tm), sizeof h); fprintf(stderr, "STK_TIMING cycles per step (wave 1 of blocks < 64): act %.0f | bar %.0f | book+bar %.0f | out %.0f | bar %.0f\n",
-      h[0] / (9.0 * 64 * io.T), h[1] / (9.0 * 64 * io.T), h[2] / (9.0 * 64 * io.T), h[3] / (9.0 * 64 * io.T), h[4] / (9.0 * 64 * io.T)); }
-    if (getenv("PHX_TIMING_DUMP") && calls >= 8 && calls <= 10) {
-      if (calls > 8) { (void)hipDeviceSynchronize(); unsigned long long r[8]; (void)hipMemcpyFromSymbol(r, HIP_SYMBOL(g_stk_rt), sizeof r); const double n = (double)r[5];
-        fprintf(stderr, "STK_RT launch %d: wall %.1f us | per block: setup %.2f loop %.2f epilogue %.2f us | blocks %.0f\n", calls - 1, (r[1] - r[0]) * 0.01, r[2] * 0.01 / n, r[3] * 0.01 / n, r[4] * 0.01 / n, n); }
-      unsigned long long z[8] = {~0ull, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stk_rt), z, sizeof z); } }
-#endif
   // threads per env: a block whose STKR_SLOTS passes cover the agents
-  const int nt_env = phx_knobs().stk_rollout_nt;
   // (1 152 agents: 384 threads with three full slots 35.4 us per step, 33.0 with the registers capped for 5 blocks per CU;
   //  512 threads -- 32 waves per CU, a quarter of the lanes idle in the third slot -- 28.1: the step is a latency chain)
   int nt = 1024;
   for (int cand : {128, 256, 512, 1024}) if (STKR_SLOTS * cand >= sp.A) { nt = cand; break; }
-  if (nt_env && STKR_SLOTS * nt_env >= sp.A) nt = nt_env;
   if (STKR_SLOTS * nt < sp.A) return hipErrorInvalidConfiguration;
   const size_t lds = phx_stk_rollout_lds(sp);
   phx_note_kernel("phx_stk_rollout_kernel");
@@ -829,7 +767,6 @@ hipError_t phx_launch_stk_rollout(const DevSpec& sp, const phx_rollout_io& io, h
   switch (nt) {
     case 128: PHX_LAUNCH_STKR(128); break;
     case 256: PHX_LAUNCH_STKR(256); break;
-    case 384: PHX_LAUNCH_STKR(384); break;
     case 512: PHX_LAUNCH_STKR(512); break;
     default: PHX_LAUNCH_STKR(1024); break;
   }
@@ -853,26 +790,16 @@ __global__ __launch_bounds__(256) void phx_stk_materialise_kernel(const DevSpec 
 }
 
 hipError_t phx_launch_stk_step(const DevSpec& sp, const phx_step_io& io, hipStream_t st) {
-#ifdef PHX_TIMING
-  { static int calls = 0; if (getenv("PHX_TIMING_DUMP") && ++calls == 101) { (void)hipDeviceSynchronize(); unsigned long long h[8];
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stk_tm), sizeof h); const double n = 100.0 * 64;
-      fprintf(stderr, "STK_STEP_TIMING cycles (wave 1 of blocks < 64): loads+bar %.0f | act %.0f | bar %.0f | book %.0f | bar %.0f | out %.0f\n",
-              h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n); } }
-#endif
   const int nSell = sp.kind_count[PHX_KIND_SELLER];
   const int nBuy = sp.kind_count[PHX_KIND_BUYER];
   const size_t lds = g_stk_paid_off(nSell) + (size_t)nBuy * 8 + (((size_t)nBuy + 15) & ~(size_t)15) + 32 + (sp.dynamic_graph ? (size_t)sp.n_conn : 0);
-  const int fast_env = phx_knobs().stk_step_fast;
-  const int nt_env = phx_knobs().stk_step_nt;
-  if (sp.stk_packed && fast_env && sp.A <= STKR_SLOTS * 1024) {
+  if (sp.stk_packed && sp.A <= STKR_SLOTS * 1024) {
     int nt = 1024;
     for (int cand : {128, 256, 512, 1024}) if (STKR_SLOTS * cand >= sp.A) { nt = cand; break; }
-    if (nt_env && STKR_SLOTS * nt_env >= sp.A) nt = nt_env;
     phx_note_kernel("phx_stk_step_fast_kernel");
     switch (nt) {
       case 128: hipLaunchKernelGGL((phx_stk_step_fast_kernel<128>), dim3(sp.B), dim3(128), lds, st, sp, io); break;
       case 256: hipLaunchKernelGGL((phx_stk_step_fast_kernel<256>), dim3(sp.B), dim3(256), lds, st, sp, io); break;
-      case 384: hipLaunchKernelGGL((phx_stk_step_fast_kernel<384>), dim3(sp.B), dim3(384), lds, st, sp, io); break;
       case 512: hipLaunchKernelGGL((phx_stk_step_fast_kernel<512>), dim3(sp.B), dim3(512), lds, st, sp, io); break;
       default: hipLaunchKernelGGL((phx_stk_step_fast_kernel<1024>), dim3(sp.B), dim3(1024), lds, st, sp, io); break;
     }

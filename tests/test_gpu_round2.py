@@ -353,7 +353,7 @@ def test_fast_rollout_kernel_edge_cases_match_oracle(S, K, B, num_steps):
 @pytest.mark.parametrize("S,K,B,num_steps", [(9, 6, 64, 100), (51, 4, 16, 100), (3, 2, 48, 7), (5, 1, 40, 33)])
 def test_fsm_lean_rollout_loop_edge_cases_match_oracle(S, K, B, num_steps):
     """device-RNG rollouts of FSM supply chains whose shops all have the same 1..6 customers (at these sizes the time-parallel
-    kernel of phx_sc_rollout_fsm.hip; PHX_FSM_FAST=0: the lean loop of phx_sc_fused.hip; PHX_FSM_LEAN=0: the general one):
+    kernel of phx_sc_rollout_fsm.hip; per env, variants={"rollout": "lean"}: the lean loop of phx_sc_fused.hip; "general": the general one):
     fragments starting on ticks that are no multiple of 4 and in
     either stage, several episode ends per fragment, caches carried across launches, stocks poked outside [0, 100] (the
     observation tables do not cover them), hand-over to per-step launches."""

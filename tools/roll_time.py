@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Time phx_rollout launches of one supply-chain config (event pair over N back-to-back launches) and print a
-checksum of the fragment, so kernel variants (env knobs, alternative .so via PHX_LIB) can be A/B-compared in one
-gpurun call.   python tools/roll_time.py [--shops 9 --cust 6 --batch 4096 --T 100 --n 200 --fsm]"""
+checksum of the fragment, so kernel variants (--rollout / --block: phx_spec.variant_*; an alternative .so via PHX_LIB_PATH) can be
+A/B-compared in one run.   python tools/roll_time.py [--shops 9 --cust 6 --batch 4096 --T 100 --n 200 --fsm]"""
 import argparse, hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
