@@ -412,6 +412,47 @@ typedef struct phx_policy_mlp {
   const float* b[3];           /* device: [width0], [width1] (or [1]), [1]                  */
 } phx_policy_mlp;
 
+/* ABI 10, additive: GAUSSIAN EXPLORATION of a device policy (RLlib's DiagGaussian for a Box action space, explore = True).  The head's
+ * log-std output, a correctly rounded f32 exp, the draw and its log-density are DEFINED here, every operation a correctly rounded f32
+ * one (numpy restates it bit for bit: tests/policy_explore_ref.py):
+ *     y  = the network's output unit (above);  ls = b_log_std[0];  for k = 0 .. width[last]-1 ascending: ls = fmaf(w_log_std[k], h[k], ls)
+ *          (w_log_std == NULL: ls = b_log_std[0]).  y and ls then enter as y + 0.0f and ls + 0.0f (an exact zero is +0: the kernels pad
+ *          hidden layers with zero units, which may turn a -0 sum into +0)
+ *     l  = ls < PHX_LOG_STD_MIN ? PHX_LOG_STD_MIN : (ls > PHX_LOG_STD_MAX ? PHX_LOG_STD_MAX : ls)
+ *     std = exp(l):  n = rint(l * PHX_EXP_LOG2E) (half to even);  r = fmaf(-n, PHX_EXP_LN2_HI, l);  r = fmaf(-n, PHX_EXP_LN2_LO, r);
+ *                    p = PHX_EXP_C7;  p = fmaf(p, r, PHX_EXP_C6);  ...  p = fmaf(p, r, PHX_EXP_C0);   std = ldexp(p, n)  (exact: |n| <= 29)
+ *                    (within 0.92 ulp of exp over [-20, 20]: tests/test_policy_explore_cpu.py)
+ *     z  = fmaf(std, noise, y)                                         the raw draw, RLlib's SampleBatch "actions"
+ *     action = clip(fmaf(out_scale, z, out_bias), out_lo, out_hi) + 0.0f      (the deterministic closing, on z)
+ *     logp = fmaf(-0.5f, noise * noise, (-l) - PHX_HALF_LN_2PI)         the 1-D Gaussian log-density of z, "action_logp"
+ *     dist_inputs = (y, ls)                                            unclamped, "action_dist_inputs"
+ * noise == 0: z == y and the action is the deterministic rollout's, bit for bit.  All six pointers are device pointers, 4-byte aligned,
+ * required except w_log_std; NULL or misaligned: PHX_EINVAL.  `explore` without `policy`: PHX_EINVAL (a library older than this
+ * refuses a non-NULL reserved_ptr with PHX_EINVAL too).  Served by phx_sc_rollout_policy_explore_kernel, for the ReLU / hard-tanh
+ * kernel's policies, and by phx_sc_rollout_policy_mfma_explore_kernel, for tanh, wide layers and PHX_VR_POLICY_MFMA.  */
+#define PHX_LOG_STD_MIN  (-20.0f)
+#define PHX_LOG_STD_MAX  20.0f
+#define PHX_EXP_LOG2E    0x1.715476p+0f
+#define PHX_EXP_LN2_HI   0x1.62e430p-1f       /* ln 2 rounded to f32 */
+#define PHX_EXP_LN2_LO  -0x1.05c610p-29f      /* ln 2 - PHX_EXP_LN2_HI, rounded to f32 */
+#define PHX_EXP_C0       0x1p+0f              /* C_k = 1 / k!, rounded to f32 */
+#define PHX_EXP_C1       0x1p+0f
+#define PHX_EXP_C2       0x1p-1f
+#define PHX_EXP_C3       0x1.555556p-3f
+#define PHX_EXP_C4       0x1.555556p-5f
+#define PHX_EXP_C5       0x1.111112p-7f
+#define PHX_EXP_C6       0x1.6c16c2p-10f
+#define PHX_EXP_C7       0x1.a01a02p-13f
+#define PHX_HALF_LN_2PI  0x1.d67f1cp-1f       /* ln(2 pi) / 2 */
+typedef struct phx_policy_explore {
+  const float* noise;          /* [T][B][S]    standard-normal draws (finite), e.g. torch.randn; read during the launch   */
+  const float* w_log_std;      /* [width_last] the head's log-std row (torch: last Linear weight[1]), or NULL: state-independent */
+  const float* b_log_std;      /* [1]          torch: bias[1], or RLlib's free_log_std parameter                         */
+  float* raw_action;           /* [T][B][S]    z, RLlib's SampleBatch "actions"                                          */
+  float* logp;                 /* [T][B][S]    "action_logp"                                                             */
+  float* dist_inputs;          /* [T][B][S][2] (y, ls) unclamped, "action_dist_inputs"                                   */
+} phx_policy_explore;
+
 typedef struct phx_rollout_io {
   int32_t T;
   int32_t hints;               /* PHX_RH_* below, 0 = none                                  */
@@ -432,7 +473,10 @@ typedef struct phx_rollout_io {
    * generic engine's launch loop); both NULL = not recorded.                               */
   phx_msg_rec* msg_log;        /* [T][B][trace_cap] or NULL                                 */
   int32_t*  msg_count;         /* [T][B] or NULL                                            */
-  void*     reserved_ptr;      /* NULL (ABI 7-8: the record layout, removed in ABI 9)       */
+  union {                      /* NULL (ABI 7-8: the record layout, removed in ABI 9), or (ABI 10, additive) */
+    void*     reserved_ptr;
+    const struct phx_policy_explore* explore;   /* Gaussian exploration of `policy` (a HOST struct, read during the call) */
+  };
   /* ABI 9: a fragment LIST.  n_frag >= 2 (<= PHX_MAX_FRAGMENTS) and frags != NULL (a HOST array, read during the call): the launch
    * advances the envs T steps as always and writes rows [f T / n_frag, (f + 1) T / n_frag) to frags[f] (T % n_frag == 0; obs,
    * action_out, reward, terminated, truncated, obs_valid, reward_valid of the io itself must then be NULL; actions / exo / msg_log /

@@ -105,7 +105,13 @@ class PhxPolicyMLP(C.Structure):
                 ("w", C.c_void_p * 3), ("b", C.c_void_p * 3)]
 
 
+class PhxPolicyExplore(C.Structure):
+    """phx_policy_explore (ABI 10, additive): Gaussian exploration of the rollout's policy, passed in phx_rollout_io.reserved_ptr"""
+    _fields_ = [(n, C.c_void_p) for n in ("noise", "w_log_std", "b_log_std", "raw_action", "logp", "dist_inputs")]
+
+
 ACT_RELU, ACT_HARD_TANH, ACT_TANH = 0, 1, 2
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 20.0
 POLICY_MAX_WIDTH = 64
 POLICY_WIDE_MAX, POLICY_WIDE_STEP = 256, 32
 

@@ -1280,8 +1280,10 @@ static int rollout_impl(phx_env* e, const phx_rollout_io* io, void* stream) {
   if (!e || !io) return fail(PHX_EINVAL, "null argument");
   if (e->d.env_type != PHX_ENV_PLAIN && !(io->n_frag >= 2 || io->frags) && (!io->obs_valid || !io->reward_valid))
     return fail(PHX_EINVAL, "FSM / Stackelberg rollouts need obs_valid and reward_valid outputs");
-  if ((io->hints & ~(PHX_RH_ACTIONS_IN_DOMAIN | PHX_RH_EXO_IN_DOMAIN)) != 0 || io->reserved_ptr)
-    return fail(PHX_EINVAL, "phx_rollout: unknown hint bits / reserved_ptr must be NULL (ABI 9 removed PHX_RH_FLAGS_ZEROED and the record layout)");
+  if ((io->hints & ~(PHX_RH_ACTIONS_IN_DOMAIN | PHX_RH_EXO_IN_DOMAIN)) != 0)
+    return fail(PHX_EINVAL, "phx_rollout: unknown hint bits (ABI 9 removed PHX_RH_FLAGS_ZEROED)");
+  if (io->explore && !io->policy)
+    return fail(PHX_EINVAL, "phx_rollout: `explore` needs `policy` (ABI 7-8's record layout in this slot was removed in ABI 9)");
   if (io->policy && (io->actions || io->n_frag >= 2 || io->frags || io->msg_log || io->msg_count))
     return fail(PHX_EINVAL, "phx_rollout: `policy` excludes replayed actions, fragment lists and message logs");
   if (io->n_frag >= 2 || io->frags) {   // ABI 9: a fragment list
@@ -1363,7 +1365,7 @@ static int rollout_impl(phx_env* e, const phx_rollout_io* io, void* stream) {
   if (io->policy) {                   // ABI 10: the policy evaluated on the device (phx_sc_policy.hip; tanh / wide / PHX_VR_POLICY_MFMA: phx_sc_policy_mfma.hip)
     if (!e->use_fused) return fail(PHX_EUNSUPPORTED, "phx_rollout: `policy` needs a plain supply-chain env on its fused schedule");
     const char* why = phx_sc_policy_unsupported(e->d, *io);
-    if (why) return fail(strstr(why, "phx_policy_mlp") ? PHX_EINVAL : PHX_EUNSUPPORTED, "phx_rollout: %s", why);
+    if (why) return fail(strstr(why, "phx_policy_") ? PHX_EINVAL : PHX_EUNSUPPORTED, "phx_rollout: %s", why);      // (phx_policy_mlp / _explore)
     if (phx_sc_policy_wants_mfma(e->d, *io)) HIPCHK(phx_launch_sc_rollout_policy_mfma(e->d, *io, (hipStream_t)stream));      // phx_sc_policy_mfma.hip
     else HIPCHK(phx_launch_sc_rollout_policy(e->d, *io, (hipStream_t)stream));
     return PHX_OK;

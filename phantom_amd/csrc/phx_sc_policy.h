@@ -13,6 +13,10 @@ struct PolArgs {
   phx_rollout_io io;
   phx_policy_mlp pol;
 };
+// the exploring kernels' arguments: the same block and the io's phx_policy_explore (a host struct) copied in by value
+struct PolArgsX : PolArgs {
+  phx_policy_explore ex;
+};
 
 // PHX_ACT_TANH as the header defines it, step for step: every operation is a correctly rounded f32 one (__fmaf_rn, __fmul_rn, __fdiv_rn),
 // so the value is the definition's on every machine
@@ -49,6 +53,38 @@ __device__ __forceinline__ float pol_action(const phx_policy_mlp& p, float y) {
   const float av = __fmaf_rn(p.out_scale, y, p.out_bias);
   return (av < p.out_lo ? p.out_lo : (av > p.out_hi ? p.out_hi : av)) + 0.0f;
 }
+
+// Gaussian exploration (include/phantom_amd.h, phx_policy_explore), step for step with correctly rounded f32 operations, like pol_tanh.
+// exp(l) for a clamped log-std |l| <= 20: Cody-Waite reduction by ln 2, a degree-7 Taylor polynomial, ldexp (exact for |n| <= 29)
+__device__ __forceinline__ float pol_exp(float l) {
+  const float n = __builtin_rintf(__fmul_rn(l, PHX_EXP_LOG2E));        // (v_rndne_f32: half to even)
+  float r = __fmaf_rn(-n, PHX_EXP_LN2_HI, l);
+  r = __fmaf_rn(-n, PHX_EXP_LN2_LO, r);
+  float p = PHX_EXP_C7;
+  p = __fmaf_rn(p, r, PHX_EXP_C6); p = __fmaf_rn(p, r, PHX_EXP_C5); p = __fmaf_rn(p, r, PHX_EXP_C4); p = __fmaf_rn(p, r, PHX_EXP_C3);
+  p = __fmaf_rn(p, r, PHX_EXP_C2); p = __fmaf_rn(p, r, PHX_EXP_C1); p = __fmaf_rn(p, r, PHX_EXP_C0);
+  return __builtin_ldexpf(p, (int)n);
+}
+
+// the Gaussian log-density of z = fmaf(std, noise, y), stated through the noise: -noise^2 / 2 - l - ln(2 pi) / 2
+__device__ __forceinline__ float pol_logp(float noise, float l) {
+  return __fmaf_rn(-0.5f, __fmul_rn(noise, noise), __fsub_rn(-l, PHX_HALF_LN_2PI));
+}
+
+// the draw: (y, ls) as the header takes them (+ 0.0f), the clamped log-std, z, the env's action and log-density
+struct PolDraw { float y, ls, z, logp, action; };
+__device__ __forceinline__ PolDraw pol_draw(const phx_policy_mlp& p, float y, float ls, float noise) {
+  PolDraw d;
+  d.y = y + 0.0f; d.ls = ls + 0.0f;
+  const float l = d.ls < PHX_LOG_STD_MIN ? PHX_LOG_STD_MIN : (d.ls > PHX_LOG_STD_MAX ? PHX_LOG_STD_MAX : d.ls);
+  d.z = __fmaf_rn(pol_exp(l), noise, d.y);
+  d.logp = pol_logp(noise, l);
+  d.action = pol_action(p, d.z);
+  return d;
+}
+
+// dist_inputs' (y, ls): one 8-byte store at a 4-byte aligned address (phx_policy_explore asks for 4 bytes)
+typedef float pol_f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 // One (env, shop) row of a plain supply-chain env: its state lives in registers for the launch.
 struct PolShop {

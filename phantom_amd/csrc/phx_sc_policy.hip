@@ -37,6 +37,15 @@ __host__ __device__ inline int pol_img_floats(int n_hidden, int W0p, int W1p) {
   return n_hidden == 1 ? 4 * W0p + W0p + 4 : 4 * W0p + W1p * W0p + W1p + W1p + 4;
 }
 
+// EXPLORE: the log-std output's eight terms of a second-layer block, from the same pre-activations as y's, k ascending
+template <int ACT>
+__device__ __forceinline__ float pol_ls8(const float* wl, const float* c, float ls) {
+  const float4 la = *(const float4*)wl, lb = *(const float4*)(wl + 4);
+  ls = __fmaf_rn(la.x, pol_act<ACT>(c[0]), ls); ls = __fmaf_rn(la.y, pol_act<ACT>(c[1]), ls); ls = __fmaf_rn(la.z, pol_act<ACT>(c[2]), ls); ls = __fmaf_rn(la.w, pol_act<ACT>(c[3]), ls);
+  ls = __fmaf_rn(lb.x, pol_act<ACT>(c[4]), ls); ls = __fmaf_rn(lb.y, pol_act<ACT>(c[5]), ls); ls = __fmaf_rn(lb.z, pol_act<ACT>(c[6]), ls); ls = __fmaf_rn(lb.w, pol_act<ACT>(c[7]), ls);
+  return ls;
+}
+
 // NT threads per workgroup: 256 with one hidden layer; 128 with two (the first layer's activations live in a wave-private LDS column
 // per lane, [unit][lane]: bank-conflict free -- a register array cannot be indexed by a run-time width)
 // EXO: the order sizes are replayed from io.exo (global loads inside the step loop); the device-drawn instantiation has NO load in its loop, so
@@ -45,14 +54,20 @@ __host__ __device__ inline int pol_img_floats(int n_hidden, int W0p, int W1p) {
 // through the scalar cache (s_load_dwordx8 from torch's own [W1][W0] layout), 32 fused multiply-adds on four independent chains; LDS then
 // carries the first layer's activations only (one 4-byte read per lane and k, shared by the four rows).  The LDS form reads every weight as
 // a broadcast: 64 lanes x 4 bytes of LDS return bandwidth per multiply-add -- the layer was LDS-bound (32 us per step for 3-64-64-1).
-template <int ACT, bool TWO, int NT, bool EXO, bool SW>
-__global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs a) {
+// EXPLORE (phx_policy_explore, A = PolArgsX): the head's log-std row follows the image -- [WLp] (zero where w_log_std is NULL), its bias
+// (+ 3 pad) -- and is accumulated beside y from the same activations; the step's noise is loaded before the previous step's trajectory
+// stores are issued, so that its wait does not drain them.  The body is one template: the kernels below instantiate it with EXPLORE =
+// false (phx_sc_rollout_policy_kernel) and true (phx_sc_rollout_policy_explore_kernel).
+template <int ACT, bool TWO, int NT, bool EXO, bool SW, bool EXPLORE, class A>
+__device__ __forceinline__ void pol_rollout_valu(const A& a) {
   extern __shared__ __attribute__((aligned(16))) float s_img[];
   const int tid = threadIdx.x, S = a.S;
   const int W0 = a.pol.width[0], W1 = TWO ? a.pol.width[1] : 0;
   const int W0p = (W0 + 7) & ~7, W1p = (W1 + 7) & ~7;
   const int n_img = pol_img_floats(TWO ? 2 : 1, W0p, W1p);
-  float* const s_h = s_img + n_img;                                    // TWO: [W0p][NT]
+  const int WLp = TWO ? W1p : W0p;
+  float* const s_ls = s_img + n_img;                                   // EXPLORE: the log-std row [WLp], its bias (+ 3 pad)
+  float* const s_h = s_img + n_img + (EXPLORE ? WLp + 4 : 0);          // TWO: [W0p][NT]
   {                                                                    // stage the network
     for (int i = tid; i < W0p; i += NT) {
       const bool in = i < W0;
@@ -68,6 +83,11 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
       float* ob1 = o1 + W1p * W0p; float* ow2 = ob1 + W1p;
       for (int i = tid; i < W1p; i += NT) { ob1[i] = i < W1 ? a.pol.b[1][i] : 0.0f; ow2[i] = i < W1 ? a.pol.w[2][i] : 0.0f; }
       if (tid < 4) ow2[W1p + tid] = tid == 0 ? a.pol.b[2][0] : 0.0f;
+    }
+    if constexpr (EXPLORE) {
+      const int WL = TWO ? W1 : W0;
+      const float* const wls = a.ex.w_log_std;
+      for (int i = tid; i < WLp + 4; i += NT) s_ls[i] = (wls && i < WL) ? wls[i] : (i == WLp ? a.ex.b_log_std[0] : 0.0f);
     }
   }
   const int b0 = (int)blockIdx.x * a.epb;                              // the workgroup's first env
@@ -89,6 +109,12 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
   float* p_obs = a.io.obs + pair * 3; float* p_act = a.io.action_out + pair; float* p_rew = a.io.reward + pair;
   const bool has_ter = a.io.terminated != nullptr;                     // (uniform: a scalar branch)
   uint8_t* p_ter = a.io.terminated + pair; uint8_t* p_tru = a.io.truncated + pair;
+  // EXPLORE: running pointers of the noise and the three planes; `nz` is the step's noise, loaded one step ahead
+  const float* p_nz = nullptr; float *p_raw = nullptr, *p_lp = nullptr, *p_di = nullptr; float nz = 0.0f;
+  if constexpr (EXPLORE) {
+    p_nz = a.ex.noise + pair; p_raw = a.ex.raw_action + pair; p_lp = a.ex.logp + pair; p_di = a.ex.dist_inputs + pair * 2;
+    if (on) nz = *p_nz;
+  }
   for (int t = 0; t < a.T; ++t) {
     // ---- compute_action: the MLP on the previous observation (phx_policy_mlp, include/phantom_amd.h) --------------------------------
     // two units per packed fused multiply-add (each element is the fmaf of the definition)
@@ -100,9 +126,10 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
       c = __builtin_elementwise_fma((pol_f2){v.x, v.y}, (pol_f2){x[2], x[2]}, c);
       ha = pol_act<ACT>(c.x); hb = pol_act<ACT>(c.y);
     };
-    float y;
+    float y, ls = 0.0f;                                                // (ls: EXPLORE's log-std output, beside y)
     if (!TWO) {
       y = o1[W0p];
+      if constexpr (EXPLORE) ls = s_ls[W0p];
       for (int i0 = 0; i0 < W0p; i0 += 8) {                            // eight units at a time: their reads are in flight together
         float h[8];
 #pragma unroll
@@ -110,6 +137,11 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
         const float4 wa = *(const float4*)(o1 + i0), wb = *(const float4*)(o1 + i0 + 4);
         y = __fmaf_rn(wa.x, h[0], y); y = __fmaf_rn(wa.y, h[1], y); y = __fmaf_rn(wa.z, h[2], y); y = __fmaf_rn(wa.w, h[3], y);      // ascending unit order
         y = __fmaf_rn(wb.x, h[4], y); y = __fmaf_rn(wb.y, h[5], y); y = __fmaf_rn(wb.z, h[6], y); y = __fmaf_rn(wb.w, h[7], y);
+        if constexpr (EXPLORE) {
+          const float4 la = *(const float4*)(s_ls + i0), lb = *(const float4*)(s_ls + i0 + 4);
+          ls = __fmaf_rn(la.x, h[0], ls); ls = __fmaf_rn(la.y, h[1], ls); ls = __fmaf_rn(la.z, h[2], ls); ls = __fmaf_rn(la.w, h[3], ls);
+          ls = __fmaf_rn(lb.x, h[4], ls); ls = __fmaf_rn(lb.y, h[5], ls); ls = __fmaf_rn(lb.z, h[6], ls); ls = __fmaf_rn(lb.w, h[7], ls);
+        }
       }
     } else {
       for (int i0 = 0; i0 < W0p; i0 += 8) {
@@ -121,6 +153,7 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
       }
       const float* const ob1 = o1 + W1p * W0p; const float* const ow2 = ob1 + W1p;
       y = ow2[W1p];
+      if constexpr (EXPLORE) ls = s_ls[W1p];
       if (SW && ((W0 | W1) & 7) == 0) {
         // eight units x eight k per trip: 64 weights in SGPRs (eight s_load_dwordx8 in flight together), 64 v_fmac_f32 with an SGPR operand on
         // eight independent chains (ascending k each) -- no packing moves, one scalar-cache and one LDS round trip per 64 multiply-adds
@@ -148,6 +181,7 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
           const float4 wa = *(const float4*)(ow2 + j0), wb = *(const float4*)(ow2 + j0 + 4);
           y = __fmaf_rn(wa.x, pol_act<ACT>(c[0]), y); y = __fmaf_rn(wa.y, pol_act<ACT>(c[1]), y); y = __fmaf_rn(wa.z, pol_act<ACT>(c[2]), y); y = __fmaf_rn(wa.w, pol_act<ACT>(c[3]), y);
           y = __fmaf_rn(wb.x, pol_act<ACT>(c[4]), y); y = __fmaf_rn(wb.y, pol_act<ACT>(c[5]), y); y = __fmaf_rn(wb.z, pol_act<ACT>(c[6]), y); y = __fmaf_rn(wb.w, pol_act<ACT>(c[7]), y);
+          if constexpr (EXPLORE) ls = pol_ls8<ACT>(s_ls + j0, c, ls);
         }
       } else if (SW) {
         typedef const __attribute__((address_space(4))) float* pol_cfp;
@@ -169,6 +203,10 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
           }
           const float4 wo = *(const float4*)(ow2 + j0);
           y = __fmaf_rn(wo.x, pol_act<ACT>(c0), y); y = __fmaf_rn(wo.y, pol_act<ACT>(c1), y); y = __fmaf_rn(wo.z, pol_act<ACT>(c2), y); y = __fmaf_rn(wo.w, pol_act<ACT>(c3), y);
+          if constexpr (EXPLORE) {
+            const float4 lo = *(const float4*)(s_ls + j0);
+            ls = __fmaf_rn(lo.x, pol_act<ACT>(c0), ls); ls = __fmaf_rn(lo.y, pol_act<ACT>(c1), ls); ls = __fmaf_rn(lo.z, pol_act<ACT>(c2), ls); ls = __fmaf_rn(lo.w, pol_act<ACT>(c3), ls);
+          }
         }
       } else
       for (int j0 = 0; j0 < W1p; j0 += 8) {                            // eight units of the second layer: eight independent chains over k
@@ -187,26 +225,43 @@ __global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs
         const float4 wa = *(const float4*)(ow2 + j0), wb = *(const float4*)(ow2 + j0 + 4);
         y = __fmaf_rn(wa.x, pol_act<ACT>(c[0]), y); y = __fmaf_rn(wa.y, pol_act<ACT>(c[1]), y); y = __fmaf_rn(wa.z, pol_act<ACT>(c[2]), y); y = __fmaf_rn(wa.w, pol_act<ACT>(c[3]), y);
         y = __fmaf_rn(wb.x, pol_act<ACT>(c[4]), y); y = __fmaf_rn(wb.y, pol_act<ACT>(c[5]), y); y = __fmaf_rn(wb.z, pol_act<ACT>(c[6]), y); y = __fmaf_rn(wb.w, pol_act<ACT>(c[7]), y);
+        if constexpr (EXPLORE) ls = pol_ls8<ACT>(s_ls + j0, c, ls);
       }
     }
-    const float action = pol_action(a.pol, y);
+    PolDraw dr;
+    if constexpr (EXPLORE) dr = pol_draw(a.pol, y, a.ex.w_log_std ? ls : s_ls[WLp], nz);     // (no row: ls = b_log_std[0])
+    const float action = EXPLORE ? dr.action : pol_action(a.pol, y);
 
     // ---- PhantomEnv.step for the pair (env.py:239-303 with the supply chain's closed form) -------------------------------------------
     const int D = sh.orders<EXO>(a, t, b, s);
     float ob[3], rw;
     const bool trunc = sh.advance(a, action, D, ob, rw);
     if (on) {                                                          // the trajectory row, rollout.py:361-389 (running pointers: one 64-bit add per plane and step)
+      if constexpr (EXPLORE) {                                         // the next step's noise, issued ahead of this step's stores
+        p_nz += total;
+        if (t + 1 < a.T) nz = *p_nz;
+      }
       p_obs[0] = ob[0]; p_obs[1] = ob[1]; p_obs[2] = ob[2];
       *p_act = action;
       *p_rew = rw;
       if (has_ter) { *p_ter = 0; p_ter += total; }
       *p_tru = trunc ? 1 : 0;
       p_obs += total * 3; p_act += total; p_rew += total; p_tru += total;
+      if constexpr (EXPLORE) {
+        *p_raw = dr.z; *p_lp = dr.logp; *(pol_f2u*)p_di = (pol_f2u){dr.y, dr.ls};
+        p_raw += total; p_lp += total; p_di += total * 2;
+      }
     }
     sh.next(trunc, ob, x);                                             // the caller's env.reset() at an episode's end; the next input
   }
   if (on) sh.store(a, pair, b, s, x);
 }
+
+template <int ACT, bool TWO, int NT, bool EXO, bool SW>
+__global__ __launch_bounds__(NT) void phx_sc_rollout_policy_kernel(const PolArgs a) { pol_rollout_valu<ACT, TWO, NT, EXO, SW, false>(a); }
+
+template <int ACT, bool TWO, int NT, bool EXO, bool SW>
+__global__ __launch_bounds__(NT) void phx_sc_rollout_policy_explore_kernel(const PolArgsX a) { pol_rollout_valu<ACT, TWO, NT, EXO, SW, true>(a); }
 
 // host: serves the call?  (plain supply chain on the fused schedule, ShopAgent observations, whole envs in a 256-lane workgroup)
 const char* phx_sc_policy_unsupported(const DevSpec& sp, const phx_rollout_io& io) {
@@ -222,6 +277,12 @@ const char* phx_sc_policy_unsupported(const DevSpec& sp, const phx_rollout_io& i
     return "phx_policy_mlp: unknown activation (PHX_ACT_RELU, PHX_ACT_HARD_TANH or PHX_ACT_TANH)";
   for (int l = 0; l <= p.n_hidden; ++l) if (!p.w[l] || !p.b[l] || ((uintptr_t)p.w[l] & 3u) || ((uintptr_t)p.b[l] & 3u)) return "phx_policy_mlp: a weight / bias pointer is NULL or misaligned";
   if (!(p.out_lo >= 0.0f) || !(p.out_hi >= p.out_lo)) return "phx_policy_mlp: 0 <= out_lo <= out_hi (ShopAgent's action space)";
+  if (io.explore) {
+    const phx_policy_explore& x = *io.explore;
+    const void* need[] = {x.noise, x.b_log_std, x.raw_action, x.logp, x.dist_inputs};
+    for (const void* q : need) if (!q || ((uintptr_t)q & 3u)) return "phx_policy_explore: a required pointer is NULL or not 4-byte aligned";
+    if ((uintptr_t)x.w_log_std & 3u) return "phx_policy_explore: w_log_std is not 4-byte aligned";
+  }
   return nullptr;
 }
 
@@ -235,29 +296,36 @@ bool phx_sc_policy_wants_mfma(const DevSpec& sp, const phx_rollout_io& io) {
 }
 
 hipError_t phx_launch_sc_rollout_policy(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st) {
-  PolArgs a; memset(&a, 0, sizeof a);
+  PolArgsX a; memset(&a, 0, sizeof a);
   a.B = sp.B; a.S = sp.S; a.T = io.T; a.num_steps = sp.num_steps; a.n_exo = sp.n_exo;
   a.seed = sp.seed; a.env_offset = sp.env_offset;
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES]; a.missed = (int32_t*)sp.f[F_SHOP_MISSED];
   a.delivered = (int32_t*)sp.f[F_SHOP_DELIVERED]; a.env_step = (int32_t*)sp.f[F_ENV_STEP]; a.env_tick = (int32_t*)sp.f[F_ENV_TICK];
   a.shop_norm = sp.shop_norm; a.shop_cust_ptr = sp.shop_cust_ptr; a.shop_cust_exo = sp.shop_cust_exo;
   a.io = io; a.pol = *io.policy;
+  const bool explore = io.explore != nullptr;
+  if (explore) a.ex = *io.explore;
   const bool two = a.pol.n_hidden == 2;
   const int NT = two ? 128 : 256;
   a.epb = NT / sp.S;
   const dim3 grid((unsigned)((sp.B + a.epb - 1) / a.epb));
   const int W0p = (a.pol.width[0] + 7) & ~7, W1p = two ? (a.pol.width[1] + 7) & ~7 : 0;
   const int n_img = pol_img_floats(a.pol.n_hidden, W0p, W1p);
-  const size_t lds = (size_t)n_img * 4 + (two ? (size_t)W0p * NT * sizeof(float) : 0);      // <= 18.7 + 32 KB
-  phx_note_kernel("phx_sc_rollout_policy_kernel");
+  const int WLp = two ? W1p : W0p;
+  const size_t lds = (size_t)n_img * 4 + (explore ? (size_t)(WLp + 4) * 4 : 0) + (two ? (size_t)W0p * NT * sizeof(float) : 0);      // <= 18.7 + 0.3 + 32 KB
+  phx_note_kernel(explore ? "phx_sc_rollout_policy_explore_kernel" : "phx_sc_rollout_policy_kernel");
   const bool sw = two && (a.pol.width[0] & 7) == 0 && (a.pol.width[1] & 3) == 0;
+  const PolArgs& a0 = a;                                               // (the deterministic kernels take the base block)
+#define POL_GO(ACT_, TWO_, NT_, EXO_, SW_) do { \
+    if (explore) hipLaunchKernelGGL((phx_sc_rollout_policy_explore_kernel<ACT_, TWO_, NT_, EXO_, SW_>), grid, dim3(NT_), lds, st, a); \
+    else hipLaunchKernelGGL((phx_sc_rollout_policy_kernel<ACT_, TWO_, NT_, EXO_, SW_>), grid, dim3(NT_), lds, st, a0); } while (0)
 #define POL_LAUNCH(ACT_, TWO_, NT_) do { \
-    if (TWO_ && sw) { if (io.exo) hipLaunchKernelGGL((phx_sc_rollout_policy_kernel<ACT_, TWO_, NT_, true, TWO_>), grid, dim3(NT_), lds, st, a); \
-                      else hipLaunchKernelGGL((phx_sc_rollout_policy_kernel<ACT_, TWO_, NT_, false, TWO_>), grid, dim3(NT_), lds, st, a); } \
-    else if (io.exo) hipLaunchKernelGGL((phx_sc_rollout_policy_kernel<ACT_, TWO_, NT_, true, false>), grid, dim3(NT_), lds, st, a); \
-    else hipLaunchKernelGGL((phx_sc_rollout_policy_kernel<ACT_, TWO_, NT_, false, false>), grid, dim3(NT_), lds, st, a); } while (0)
+    if (TWO_ && sw) { if (io.exo) POL_GO(ACT_, TWO_, NT_, true, TWO_); else POL_GO(ACT_, TWO_, NT_, false, TWO_); } \
+    else if (io.exo) POL_GO(ACT_, TWO_, NT_, true, false); \
+    else POL_GO(ACT_, TWO_, NT_, false, false); } while (0)
   if (a.pol.activation == PHX_ACT_HARD_TANH) { if (two) POL_LAUNCH(PHX_ACT_HARD_TANH, true, 128); else POL_LAUNCH(PHX_ACT_HARD_TANH, false, 256); }
   else { if (two) POL_LAUNCH(PHX_ACT_RELU, true, 128); else POL_LAUNCH(PHX_ACT_RELU, false, 256); }
 #undef POL_LAUNCH
+#undef POL_GO
   return hipGetLastError();
 }

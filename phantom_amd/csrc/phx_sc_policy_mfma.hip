@@ -43,8 +43,12 @@ __device__ __forceinline__ int mf_hidx(int u, int r) { return u * NR + (r ^ ((u 
 
 // ACT: PHX_ACT_*; TWO: two hidden layers; EXO: replayed order sizes; NR: rows per workgroup (64 or 128); VEC: W0 % 4 == 0 and w[1] 16-byte
 // aligned (one 16-byte load per lane and four k; otherwise four guarded 4-byte loads)
-template <int ACT, bool TWO, bool EXO, int NR, bool VEC>
-__global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const PolArgs a) {
+// EXPLORE (phx_policy_explore, A = PolArgsX): a second output row, the head's log-std row [WLp] (zero where w_log_std is NULL) and its
+// bias (+ 3 pad), after the layout's end; the output layer accumulates it beside y from the same image reads.  The step's noise is loaded
+// one step ahead, before the row's trajectory stores.  One template body: phx_sc_rollout_policy_mfma_kernel instantiates it with EXPLORE =
+// false, phx_sc_rollout_policy_mfma_explore_kernel with true.
+template <int ACT, bool TWO, bool EXO, int NR, bool VEC, bool EXPLORE, class A>
+__device__ __forceinline__ void pol_rollout_mfma(const A& a) {
   extern __shared__ __attribute__((aligned(16))) float s_mem[];
   constexpr int NTILE = NR / 32;                 // 32-row tiles of an MFMA
   const int tid = threadIdx.x, S = a.S, lane = tid & 63, wave = tid >> 6, hl = lane >> 5, l32 = lane & 31;
@@ -62,6 +66,10 @@ __global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const
     const int WL = TWO ? W1 : W0, ll = TWO ? 2 : 1;
     for (int i = tid; i < WLp + 4; i += MF_NT) s_wl[i] = i < WL ? a.pol.w[ll][i] : (i == WLp ? a.pol.b[ll][0] : 0.0f);
     if (TWO) for (int i = tid; i < W1p; i += MF_NT) s_b1[i] = i < W1 ? a.pol.b[1][i] : 0.0f;
+    if constexpr (EXPLORE) {
+      const float* const wls = a.ex.w_log_std;
+      for (int i = tid; i < WLp + 4; i += MF_NT) s_mem[L.total + i] = (wls && i < WL) ? wls[i] : (i == WLp ? a.ex.b_log_std[0] : 0.0f);
+    }
   }
   // ---- the rows: lane tid < NR owns row tid (whole envs) --------------------------------------------------------------------------------
   const int b0 = (int)blockIdx.x * a.epb;                              // the workgroup's first env
@@ -109,6 +117,13 @@ __global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const
   float* p_obs = a.io.obs + pair * 3; float* p_act = a.io.action_out + pair; float* p_rew = a.io.reward + pair;
   const bool has_ter = a.io.terminated != nullptr;                     // (uniform: a scalar branch)
   uint8_t* p_ter = a.io.terminated + pair; uint8_t* p_tru = a.io.truncated + pair;
+  // EXPLORE: running pointers of the noise and the three planes; `nz` is the step's noise, loaded one step ahead
+  const float* const s_ls = s_mem + L.total;
+  const float* p_nz = nullptr; float *p_raw = nullptr, *p_lp = nullptr, *p_di = nullptr; float nz = 0.0f;
+  if constexpr (EXPLORE) {
+    p_nz = a.ex.noise + pair; p_raw = a.ex.raw_action + pair; p_lp = a.ex.logp + pair; p_di = a.ex.dist_inputs + pair * 2;
+    if (on) nz = *p_nz;
+  }
   for (int t = 0; t < a.T; ++t) {
     // ---- layer 0 (VALU): h0[u][r] = act(b + w.x0 + w.x1 + w.x2), k ascending ------------------------------------------------------------
     {
@@ -187,18 +202,36 @@ __global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const
         y = __fmaf_rn(w.x, s_h[mf_hidx<NR>(k0 + 0, tid)], y); y = __fmaf_rn(w.y, s_h[mf_hidx<NR>(k0 + 1, tid)], y);
         y = __fmaf_rn(w.z, s_h[mf_hidx<NR>(k0 + 2, tid)], y); y = __fmaf_rn(w.w, s_h[mf_hidx<NR>(k0 + 3, tid)], y);
       }
-      const float action = pol_action(a.pol, y);
+      PolDraw dr;
+      if constexpr (EXPLORE) {                                         // the log-std output: the same walk over the image
+        float ls = s_ls[WLp];
+        for (int k0 = 0; k0 < WLp; k0 += 4) {
+          const float4 w = *(const float4*)(s_ls + k0);
+          ls = __fmaf_rn(w.x, s_h[mf_hidx<NR>(k0 + 0, tid)], ls); ls = __fmaf_rn(w.y, s_h[mf_hidx<NR>(k0 + 1, tid)], ls);
+          ls = __fmaf_rn(w.z, s_h[mf_hidx<NR>(k0 + 2, tid)], ls); ls = __fmaf_rn(w.w, s_h[mf_hidx<NR>(k0 + 3, tid)], ls);
+        }
+        dr = pol_draw(a.pol, y, a.ex.w_log_std ? ls : s_ls[WLp], nz);      // (no row: ls = b_log_std[0])
+      }
+      const float action = EXPLORE ? dr.action : pol_action(a.pol, y);
       // ---- PhantomEnv.step for the pair ---------------------------------------------------------------------------------------------------
       const int D = sh.orders<EXO>(a, t, b, s);
       float ob[3], rw;
       const bool trunc = sh.advance(a, action, D, ob, rw);
       if (on) {                                                        // the trajectory row, rollout.py:361-389
+        if constexpr (EXPLORE) {                                       // the next step's noise, issued ahead of this step's stores
+          p_nz += total;
+          if (t + 1 < a.T) nz = *p_nz;
+        }
         p_obs[0] = ob[0]; p_obs[1] = ob[1]; p_obs[2] = ob[2];
         *p_act = action;
         *p_rew = rw;
         if (has_ter) { *p_ter = 0; p_ter += total; }
         *p_tru = trunc ? 1 : 0;
         p_obs += total * 3; p_act += total; p_rew += total; p_tru += total;
+        if constexpr (EXPLORE) {
+          *p_raw = dr.z; *p_lp = dr.logp; *(pol_f2u*)p_di = (pol_f2u){dr.y, dr.ls};
+          p_raw += total; p_lp += total; p_di += total * 2;
+        }
       }
       sh.next(trunc, ob, x);                                           // the caller's env.reset() at an episode's end; the next input
       s_x[4 * tid + 0] = x[0]; s_x[4 * tid + 1] = x[1]; s_x[4 * tid + 2] = x[2];
@@ -208,30 +241,43 @@ __global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const
   if (on) sh.store(a, pair, b, s, x);
 }
 
+template <int ACT, bool TWO, bool EXO, int NR, bool VEC>
+__global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_kernel(const PolArgs a) { pol_rollout_mfma<ACT, TWO, EXO, NR, VEC, false>(a); }
+
+template <int ACT, bool TWO, bool EXO, int NR, bool VEC>
+__global__ __launch_bounds__(MF_NT) void phx_sc_rollout_policy_mfma_explore_kernel(const PolArgsX a) { pol_rollout_mfma<ACT, TWO, EXO, NR, VEC, true>(a); }
+
 hipError_t phx_launch_sc_rollout_policy_mfma(const DevSpec& sp, const phx_rollout_io& io, hipStream_t st) {
-  PolArgs a; memset(&a, 0, sizeof a);
+  PolArgsX a; memset(&a, 0, sizeof a);
   a.B = sp.B; a.S = sp.S; a.T = io.T; a.num_steps = sp.num_steps; a.n_exo = sp.n_exo;
   a.seed = sp.seed; a.env_offset = sp.env_offset;
   a.stock = (int32_t*)sp.f[F_SHOP_STOCK]; a.sales = (int32_t*)sp.f[F_SHOP_SALES]; a.missed = (int32_t*)sp.f[F_SHOP_MISSED];
   a.delivered = (int32_t*)sp.f[F_SHOP_DELIVERED]; a.env_step = (int32_t*)sp.f[F_ENV_STEP]; a.env_tick = (int32_t*)sp.f[F_ENV_TICK];
   a.shop_norm = sp.shop_norm; a.shop_cust_ptr = sp.shop_cust_ptr; a.shop_cust_exo = sp.shop_cust_exo;
   a.io = io; a.pol = *io.policy;
+  const bool explore = io.explore != nullptr;
+  if (explore) a.ex = *io.explore;
   const bool two = a.pol.n_hidden == 2;
   const int NR = sp.S <= 64 ? 64 : 128;                                // (phx_sc_policy_unsupported: S <= 128)
   a.epb = NR / sp.S;
   const dim3 grid((unsigned)((sp.B + a.epb - 1) / a.epb));
   const int W0p = (a.pol.width[0] + 31) & ~31, W1p = two ? (a.pol.width[1] + 31) & ~31 : 0;
-  const size_t lds = (size_t)mf_layout(two, W0p, W1p, NR).total * sizeof(float);      // <= 135 KB (NR = 128, 256 units)
+  const int WLp = two ? W1p : W0p;
+  const size_t lds = ((size_t)mf_layout(two, W0p, W1p, NR).total + (explore ? WLp + 4 : 0)) * sizeof(float);      // <= 135 + 1 KB (NR = 128, 256 units)
   const bool vec = two && (a.pol.width[0] & 3) == 0 && ((uintptr_t)a.pol.w[1] & 15u) == 0;
-  phx_note_kernel("phx_sc_rollout_policy_mfma_kernel");
+  phx_note_kernel(explore ? "phx_sc_rollout_policy_mfma_explore_kernel" : "phx_sc_rollout_policy_mfma_kernel");
+  const PolArgs& a0 = a;                                               // (the deterministic kernels take the base block)
   // (more than 64 KB of dynamic LDS needs the attribute: per device and instantiation, result checked)
-#define MF_GO(EXO_, ACT_, TWO_, NR_, VEC_) do { \
+#define MF_GO1(KERNEL_, ARGS_, EXO_, ACT_, TWO_, NR_, VEC_) do { \
     static PhxPerDeviceOnce attr_done; int dev = 0; (void)hipGetDevice(&dev); \
     if (!attr_done.done(dev)) { \
-      const hipError_t ae = hipFuncSetAttribute((const void*)phx_sc_rollout_policy_mfma_kernel<ACT_, TWO_, EXO_, NR_, VEC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      const hipError_t ae = hipFuncSetAttribute((const void*)KERNEL_<ACT_, TWO_, EXO_, NR_, VEC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       if (ae != hipSuccess) return ae; \
       attr_done.mark(dev); } \
-    hipLaunchKernelGGL((phx_sc_rollout_policy_mfma_kernel<ACT_, TWO_, EXO_, NR_, VEC_>), grid, dim3(MF_NT), lds, st, a); } while (0)
+    hipLaunchKernelGGL((KERNEL_<ACT_, TWO_, EXO_, NR_, VEC_>), grid, dim3(MF_NT), lds, st, ARGS_); } while (0)
+#define MF_GO(EXO_, ACT_, TWO_, NR_, VEC_) do { \
+    if (explore) MF_GO1(phx_sc_rollout_policy_mfma_explore_kernel, a, EXO_, ACT_, TWO_, NR_, VEC_); \
+    else MF_GO1(phx_sc_rollout_policy_mfma_kernel, a0, EXO_, ACT_, TWO_, NR_, VEC_); } while (0)
 #define MF_LAUNCH(ACT_, TWO_, NR_, VEC_) do { if (io.exo) MF_GO(true, ACT_, TWO_, NR_, VEC_); else MF_GO(false, ACT_, TWO_, NR_, VEC_); } while (0)
 #define MF_NR(ACT_) do { \
     if (!two) { if (NR == 64) MF_LAUNCH(ACT_, false, 64, false); else MF_LAUNCH(ACT_, false, 128, false); } \
@@ -243,5 +289,6 @@ hipError_t phx_launch_sc_rollout_policy_mfma(const DevSpec& sp, const phx_rollou
 #undef MF_NR
 #undef MF_LAUNCH
 #undef MF_GO
+#undef MF_GO1
   return hipGetLastError();
 }

@@ -51,6 +51,10 @@ class Trajectory(NamedTuple):
     flat: "object" = None           # u8 [nbytes]: the one buffer every plane above is a section of (alloc_trajectory(flat=True))
     packed_flags: "object" = None   # u8 view of `flat`: bit-packed done flags for rollout collection (pack_done_flags)
     gather_nbytes: int = 0          # prefix of `flat` a learner needs from every rank (distributed.TrajectoryGather)
+    # an exploring rollout (rollout(noise=...), alloc_trajectory(explore=True)): RLlib's columns of a Gaussian policy
+    raw_actions: "object" = None    # f32 [T, B, S]     z = mean + exp(log_std) noise, SampleBatch "actions" (`actions` above: the env's)
+    action_logp: "object" = None    # f32 [T, B, S]     log N(z; mean, exp(log_std)), "action_logp"
+    dist_inputs: "object" = None    # f32 [T, B, S, 2]  (mean, log_std) unclamped, "action_dist_inputs"
 
 
 class DeviceError(RuntimeError):
@@ -435,9 +439,10 @@ class DeviceEnv:
         return bool(np.isin(k, (_abi.KIND_SHOP, _abi.KIND_SELLER, _abi.KIND_BUYER)).all())
 
     def alloc_trajectory(self, T: int, record_messages: bool = False, flat: bool = False,
-                         terminations: bool = True) -> Trajectory:
+                         terminations: bool = True, explore: bool = False) -> Trajectory:
         """Uninitialised device buffers for a T-step fragment (time-major).  ``record_messages``:
         also the per-step ordered message log (rollout.py:369-373, needs enable_tracking).
+        ``explore``: also the planes of an exploring rollout (raw_actions, action_logp, dist_inputs).
         ``flat``: every plane is a 256-byte aligned section of ONE buffer, ordered so that what a
         learner on another GPU needs is a prefix: obs | actions | rewards | [obs_valid | reward_valid] |
         bit-packed done flags, then (not gathered) the u8 truncations / terminations planes."""
@@ -447,6 +452,8 @@ class DeviceEnv:
         fsm = self._needs_valid_planes()
         if record_messages and self.spec.trace_cap <= 0:
             raise DeviceError("record_messages needs BatchResolver(enable_tracking=True)")
+        if explore and flat:
+            raise ValueError("alloc_trajectory: `explore` planes are not part of a flat fragment")
         if flat:
             n = T * B * S
             words = (n + 63) // 64
@@ -479,13 +486,17 @@ class DeviceEnv:
             trunc, term = flags[0], flags[1]
         else:
             trunc, term = e(T, B, S, dtype=torch.uint8), (e(T, B, S, dtype=torch.uint8) if terminations else None)
-        return Trajectory(e(T, B, S, D, dtype=torch.float32), e(T, B, S, dtype=torch.float32),
-                          e(T, B, S, dtype=torch.float32), term,
-                          trunc, e(B, S, D, dtype=torch.float32),
-                          e(T, B, S, dtype=torch.uint8) if fsm else None,
-                          e(T, B, S, dtype=torch.uint8) if fsm else None,
-                          e(T, B, self.spec.trace_cap, 16, dtype=torch.uint8) if record_messages else None,
-                          e(T, B, dtype=torch.int32) if record_messages else None)
+        tr = Trajectory(e(T, B, S, D, dtype=torch.float32), e(T, B, S, dtype=torch.float32),
+                        e(T, B, S, dtype=torch.float32), term,
+                        trunc, e(B, S, D, dtype=torch.float32),
+                        e(T, B, S, dtype=torch.uint8) if fsm else None,
+                        e(T, B, S, dtype=torch.uint8) if fsm else None,
+                        e(T, B, self.spec.trace_cap, 16, dtype=torch.uint8) if record_messages else None,
+                        e(T, B, dtype=torch.int32) if record_messages else None)
+        if explore:
+            tr = tr._replace(raw_actions=e(T, B, S, dtype=torch.float32), action_logp=e(T, B, S, dtype=torch.float32),
+                             dist_inputs=e(T, B, S, 2, dtype=torch.float32))
+        return tr
 
     def _check_rollout_buffers(self, T, actions, exo, out: Trajectory):
         """Raw pointers go straight to the kernel: every buffer is checked for dtype, shape,
@@ -530,26 +541,46 @@ class DeviceEnv:
             need("out.msg_count", out.msg_count, torch.int32, (B,))
             need("out.msg_log", out.msg_log, torch.uint8, (B, self.spec.trace_cap, 16))
 
+    def _check_explore_buffers(self, T, noise, out: Trajectory):
+        """an exploring rollout's noise and planes: contiguous f32 on the env's device, [T, B, S] ([T, B, S, 2] for dist_inputs)"""
+        torch = _torch()
+        B, S = self.B, self.S
+        for name, x, shape in (("noise", noise, (T, B, S)), ("out.raw_actions", out.raw_actions, (T, B, S)),
+                               ("out.action_logp", out.action_logp, (T, B, S)), ("out.dist_inputs", out.dist_inputs, (T, B, S, 2))):
+            if x is None:
+                raise ValueError(f"rollout: `{name}` is required with `noise` (alloc_trajectory(T, explore=True))")
+            if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous() or x.data_ptr() % 4:
+                raise ValueError(f"rollout: `{name}` must be a contiguous float32 tensor on {self.device}")
+            lead_ok = x.shape[0] == T if name == "noise" else x.shape[0] >= T
+            if x.dim() != len(shape) or not lead_ok or tuple(x.shape[1:]) != shape[1:]:
+                raise ValueError(f"rollout: `{name}` has shape {tuple(x.shape)}, expected {shape}")
+
     def rollout(self, T: int, actions=None, exo=None, out: Optional[Trajectory] = None, actions_in_domain: bool = False,
-                exo_in_domain: bool = False, policy=None) -> Trajectory:
+                exo_in_domain: bool = False, policy=None, noise=None) -> Trajectory:
         """T fused steps into ``out`` (allocated here when None); ``actions`` f32 [T, B, S] / ``exo`` u8 [T, B, n_exo] replay a recorded
         policy / recorded draws (None: the device's random policy / RNG stream).  ``actions_in_domain`` / ``exo_in_domain``: the caller
         vouches that every action rounds to >= 0 (clipped to the action space) / every exo byte is < 5 (``mt_draw`` output): a plain supply
         chain's replay then takes the store-wave kernel without a scan of the inputs (phx_rollout_io.hints).
         ``policy``: a ``phantom_amd.policy.MLPPolicy`` evaluated on the device for every (env, strategic agent) and step from the agent's
-        previous observation (phx_rollout_io.policy, ABI 10): T ON-POLICY steps in one launch (plain supply-chain envs)."""
+        previous observation (phx_rollout_io.policy, ABI 10): T ON-POLICY steps in one launch (plain supply-chain envs).
+        ``noise``: f32 [T, B, S] standard-normal draws (e.g. torch.randn) -- a stochastic ``policy`` EXPLORES with them
+        (phx_policy_explore): the env takes clip(out_scale z + out_bias), z = mean + exp(log_std) noise, and ``out.raw_actions`` /
+        ``out.action_logp`` / ``out.dist_inputs`` receive z, its log-probability and (mean, log_std)."""
         if policy is not None and actions is not None:
             raise ValueError("rollout: `policy` and replayed `actions` exclude each other")
+        if noise is not None and (policy is None or not policy.stochastic):
+            raise ValueError("rollout: `noise` needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
         owned = out is None
         if owned:
-            out = self.alloc_trajectory(T)
+            out = self.alloc_trajectory(T, explore=noise is not None)
         # The argument block of a repeated call into CALLER-owned buffers is built once.  The key is
         # the buffers' addresses and the entry holds no tensor: a fragment allocated here (out=None)
         # is never cached, so repeated env.rollout(T) calls pin nothing (a T=100 SC64 fragment is
         # ~80 MB at B=4096).
         ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else None
         sig = lambda x: (x.data_ptr(), x.numel()) if hasattr(x, "data_ptr") else None     # address AND size: a buffer freed
-        key = (T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(sig(x) for x in out[:10]) + (sig(actions), sig(exo), id(policy))    # and reallocated smaller misses
+        key = (T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(sig(x) for x in out[:10]) + (sig(actions), sig(exo), id(policy)) \
+            + ((sig(noise), sig(out.raw_actions), sig(out.action_logp), sig(out.dist_inputs)) if noise is not None else ())   # (and reallocated smaller misses)
         cached = None if owned else self._rollout_io_cache.get(key)
         if cached is None:
             self._check_rollout_buffers(T, actions, exo, out)
@@ -569,6 +600,11 @@ class DeviceEnv:
                     raise ValueError(f"rollout: the policy takes {policy.obs_dim} inputs, the env's observations have {self.D}")
                 pol_keep = policy.on(self.device)              # (device weights + the argument struct: kept alive with the cached block)
                 io.policy = C.addressof(pol_keep[2])
+                if noise is not None:
+                    self._check_explore_buffers(T, noise, out)
+                    ex = policy.explore_struct(self.device, noise, out.raw_actions, out.action_logp, out.dist_inputs)
+                    pol_keep = pol_keep + (ex,)
+                    io.reserved_ptr = C.addressof(ex)          # (phx_rollout_io.explore)
             cached = (io, C.byref(io), pol_keep, policy)
             if not owned:
                 if len(self._rollout_io_cache) >= 4:           # tiny LRU: drop the oldest entry

@@ -397,9 +397,10 @@ class PhantomEnv:
             dev.raise_errors(self.network)
         return out
 
-    def rollout(self, T: int, actions=None, exo=None, out=None):
+    def rollout(self, T: int, actions=None, exo=None, out=None, policy=None, noise=None):
         """T fused steps on the device with auto-reset at episode end (the loop of
-        utils/rllib/rollout.py:300-363 in one launch).  Returns a device Trajectory."""
+        utils/rllib/rollout.py:300-363 in one launch).  Returns a device Trajectory.
+        ``policy`` / ``noise``: an ``MLPPolicy`` evaluated on the device, exploring with ``noise`` (DeviceEnv.rollout)."""
         if exo is None and self.exogenous == "numpy" and self.spec.n_exo > 0:
             # step() in this mode consumes np.random (bit-parity with a seeded reference run); a fused rollout cannot
             # interleave with the host stream, so its draws come from the device Philox stream instead
@@ -412,12 +413,12 @@ class PhantomEnv:
             self._need_streams()
             exo = self._device().mt_draw(T)                     # the draws of the T steps from every instance's own stream
             exo_ok = True                                       # (randint(5) draws: the store-wave kernel may replay them, PHX_RH_EXO_IN_DOMAIN)
-        traj = self._device().rollout(T, actions, exo, out, exo_in_domain=exo_ok)
+        traj = self._device().rollout(T, actions, exo, out, exo_in_domain=exo_ok, policy=policy, noise=noise)
         self._sync_host_state()
         self._obs_state = ("traj", traj.last_obs)               # what the strategic agents observe now (sample() starts from it)
         return traj
 
-    def sample(self, T: int, actions=None, exo=None):
+    def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -425,9 +426,18 @@ class PhantomEnv:
 
         The fragment is produced one episode piece per launch (a piece ends where the episode ends: the kernel's auto-reset
         then leaves the NEXT episode's reset observation in ``last_obs``), transposed on the device and copied through pinned
-        host buffers.  Plain envs (every strategic agent observes every step); ``reset()`` first."""
+        host buffers.  Plain envs (every strategic agent observes every step); ``reset()`` first.
+
+        ``policy``: an ``MLPPolicy`` evaluated on the device (on-policy sampling, plain supply chains); ``explore=True`` samples its
+        Gaussian (a stochastic policy) with noise from ``torch.randn(generator=generator)`` -- without a generator the env's own, seeded
+        from (seed, env_offset), so that shards draw independently -- and the batch carries ``raw_actions`` / ``action_logp`` /
+        ``dist_inputs`` (RLlib's actions, action_logp, action_prob and action_dist_inputs columns)."""
         import torch
         from .rollout import FragmentBatch
+        if policy is not None and actions is not None:
+            raise ValueError("sample: `policy` and replayed `actions` exclude each other")
+        if explore and (policy is None or not policy.stochastic):
+            raise ValueError("sample: explore=True needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
         dev = self._device()
         if self.spec.env_type != _abi.ENV_PLAIN or dev._needs_valid_planes():
             raise NotImplementedError("PhantomEnv.sample: plain envs only (FSM / Stackelberg dicts omit keys: use rollout() and "
@@ -445,15 +455,23 @@ class PhantomEnv:
         term = torch.empty((T, B, S), dtype=torch.uint8, device=dev.device)
         trunc = torch.empty_like(term)
         t_in_ep = np.empty(T, dtype=np.int32); eps = np.empty(T, dtype=np.int64)
+        noise = raw = logp = dist = None
+        if explore:
+            gen = generator if generator is not None else self._noise_generator(dev.device)
+            noise = torch.randn((T, B, S), generator=gen, dtype=torch.float32, device=dev.device)
+            raw, logp = torch.empty_like(act), torch.empty_like(act)
+            dist = torch.empty((T, B, S, 2), dtype=torch.float32, device=dev.device)
         done, ep = 0, ep0
         while done < T:
             n = min(T - done, N - cur)
             # (a slice of the caller's tensor may start off a 16-byte boundary -- B * S * 4 or B * n_exo not a multiple of 16: fine since
             #  ABI 9, the replayed inputs are read element by element)
             piece = lambda x: None if x is None else x[done:done + n]
-            tr = self.rollout(n, piece(actions), piece(exo))
+            tr = self.rollout(n, piece(actions), piece(exo), policy=policy, noise=piece(noise))
             sl = slice(done, done + n)
             new_obs[sl], act[sl], rew[sl], term[sl], trunc[sl] = tr.observations, tr.actions, tr.rewards, tr.terminations, tr.truncations
+            if explore:
+                raw[sl], logp[sl], dist[sl] = tr.raw_actions, tr.action_logp, tr.dist_inputs
             obs[done] = cur_obs
             obs[done + 1:done + n] = tr.observations[:n - 1]
             t_in_ep[sl] = np.arange(cur, cur + n); eps[sl] = ep
@@ -464,13 +482,28 @@ class PhantomEnv:
             done += n
         self._episodes_done = ep
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device
-        host = self._to_pinned({"obs": am(obs), "new_obs": am(new_obs), "actions": am(act), "rewards": am(rew),
-                                "terminateds": am(term), "truncateds": am(trunc)})
+        cols = {"obs": am(obs), "new_obs": am(new_obs), "actions": am(act), "rewards": am(rew), "terminateds": am(term),
+                "truncateds": am(trunc)}
+        if explore:
+            cols.update(raw_actions=am(raw), action_logp=am(logp), dist_inputs=am(dist))
+        host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         return FragmentBatch(ids, host["obs"], host["new_obs"], host["actions"], host["rewards"], host["terminateds"].astype(bool),
                              host["truncateds"].astype(bool), np.broadcast_to(t_in_ep, (B, T)).copy(),
                              (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64),
-                             never_finishes_alone=dev.never_terminates())
+                             never_finishes_alone=dev.never_terminates(), raw_actions=host.get("raw_actions"),
+                             action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"))
+
+    def _noise_generator(self, device):
+        """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""
+        import torch
+        g = getattr(self, "_noise_gen", None)
+        if g is None or g.device != torch.device(device):
+            g = torch.Generator(device=device)
+            seed = np.random.SeedSequence([int(self._seed or 0) & (2 ** 63 - 1), int(self._env_offset) & (2 ** 63 - 1)])
+            g.manual_seed(int(seed.generate_state(1, np.uint64)[0]) & (2 ** 63 - 1))
+            self._noise_gen = g
+        return g
 
     def _cur_obs_tensor(self):
         """the observation the strategic agents hold right now (what reset / the last step / the last rollout returned), on the device"""

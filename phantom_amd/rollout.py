@@ -162,13 +162,17 @@ class FragmentBatch:
     ``reward_valid`` u8 [B, S, T] or None (0 absent / 1 value / 2 present-but-None, fsm.py:378)
     ``t``         i32 [B, T] step inside the episode (0-based)              ``eps_id``  i64 [B, T] episode counter * B + b
     ``stage``     i32 [B, T] or None: the stage the step ran in (``previous_stage`` after it, rollout.py:389-391)
+    an exploring policy's fragment (PhantomEnv.sample(explore=True)), else None:
+    ``raw_actions`` f32 [B, S, T] the Gaussian draw z (``actions`` stays what the env took: clip(out_scale z + out_bias))
+    ``action_logp`` f32 [B, S, T] log N(z; mean, exp(log_std))              ``dist_inputs`` f32 [B, S, T, 2] (mean, log_std)
     """
 
     COLUMNS = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
 
     def __init__(self, agent_ids, obs, new_obs, actions, rewards, terminateds, truncateds, t, eps_id,
                  obs_valid=None, new_obs_valid=None, reward_valid=None, stage=None, stage_ids=None,
-                 action_shape=(1,), never_finishes_alone: bool = True, done_valid=None):
+                 action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
+                 dist_inputs=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -177,6 +181,7 @@ class FragmentBatch:
         self.done_valid = done_valid                 # u8 [B, S, T] or None (None: every strategic agent has done flags in every step)
         self.action_shape = tuple(action_shape)
         self.never_finishes_alone = never_finishes_alone
+        self.raw_actions, self.action_logp, self.dist_inputs = raw_actions, action_logp, dist_inputs
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
     # ---- RLlib-shaped exit -------------------------------------------------------------------------------------------
@@ -185,7 +190,8 @@ class FragmentBatch:
         an agent's episode is a contiguous run, as in RLlib's per-agent trajectories.  ``policy_mapping_fn(agent_id)``
         (default: everything under ``"default_policy"``).  Agents of one policy that are consecutive in agent order come
         out as reshaped VIEWS of the host arrays (no copy); envs whose dicts omit keys (FSM / Stackelberg) drop the rows of
-        absent observations (boolean mask: a copy)."""
+        absent observations (boolean mask: a copy).  An exploring fragment's ``actions`` column is the raw draw z (what RLlib's
+        sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
         for s, aid in enumerate(self.agent_ids):
@@ -208,6 +214,11 @@ class FragmentBatch:
                 "t": np.broadcast_to(self.t[:, None, :], (B, n, T)).reshape(-1),
                 "env_id": np.broadcast_to(np.arange(B, dtype=np.int32)[:, None, None], (B, n, T)).reshape(-1),
             }
+            if self.raw_actions is not None:
+                cols["actions"] = sel(self.raw_actions).reshape((B * n * T,) + self.action_shape)
+                cols["action_logp"] = sel(self.action_logp).reshape(-1)
+                cols["action_prob"] = np.exp(cols["action_logp"])
+                cols["action_dist_inputs"] = sel(self.dist_inputs).reshape(B * n * T, -1)
             if self.obs_valid is not None:
                 keep = sel(self.obs_valid).reshape(-1).astype(bool)
                 cols = {k: v[keep] for k, v in cols.items()}

@@ -1,5 +1,6 @@
 """On-policy rollouts with the policy evaluated on the device (phx_rollout_io.policy): time per step at the bench shape.
-    python tools/policy_time.py [--wide]      (--wide: only the rows of RLlib-sized networks on phx_sc_rollout_policy_mfma_kernel)
+    python tools/policy_time.py [--wide | --explore]      (--wide: only the rows of RLlib-sized networks on phx_sc_rollout_policy_mfma_kernel;
+    --explore: SC64, B = 4096, T = 100, deterministic against exploring (a (mean, log_std) head and torch.randn noise) on both kernels)
 The wide rows report the f32 work of the network (2 * (3 W0 + W0 W1 + W1) FLOP per (env, shop) and step) against the 157 TF f32 matrix peak."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +29,23 @@ def pol(widths, seed=0, act="relu"):
 
 
 WIDE = "--wide" in sys.argv
+if "--explore" in sys.argv:
+    S, K, B, T = 9, 6, 4096, 100
+    for widths, act in (((32,), "relu"), ((64, 64), "relu"), ((256, 256), "tanh")):
+        env = supply_chain_env(S, [K] * S, 100, B, seed=1, exogenous="device")
+        d = env._device(); env.reset()
+        det, sto = pol(widths, act=act), pol(widths, act=act)
+        sto = ph.MLPPolicy(sto.weights[:-1] + [np.concatenate([sto.weights[-1], 0.1 * sto.weights[-1]])],
+                           sto.biases[:-1] + [np.concatenate([sto.biases[-1], [-0.5]]).astype(np.float32)],
+                           activation=act, out_scale=60.0, out_bias=45.0)
+        tr, trx = d.alloc_trajectory(T), d.alloc_trajectory(T, explore=True)
+        noise = torch.randn((T, B, S), device=d.device, generator=torch.Generator(device=d.device).manual_seed(0))
+        us = ev(lambda: d.rollout(T, out=tr, policy=det), 5); k0 = d.last_kernel()
+        usx = ev(lambda: d.rollout(T, out=trx, policy=sto, noise=noise), 5); k1 = d.last_kernel()
+        print(f"SC64 B=4096    policy 3-{'-'.join(map(str, widths))}-1 {act:4s} deterministic {us / T:8.3f} us/step [{k0}]  exploring "
+              f"{usx / T:8.3f} us/step [{k1}]  ratio {usx / us:.3f}", flush=True)
+        del env, d, tr, trx
+    sys.exit(0)
 for name, S, K, B in () if WIDE else (("SC64 B=4096", 9, 6, 4096), ("SC64 B=65536", 9, 6, 65536), ("SC256 B=8192", 51, 4, 8192)):
     env = supply_chain_env(S, [K] * S, 100, B, seed=1, exogenous="device")
     d = env._device(); env.reset()
