@@ -12,13 +12,14 @@
 // observation / reward-cache epilogue (fsm.py:309-380) runs on the same registers.  ROLLOUT = T steps
 // per launch with the random policy, the trajectory written as it is produced, and the caller's
 // env.reset() (sampler redraw included) folded in; otherwise one step in phx_step_io's layout.
-// phx_api.hip's derive() decides whether an env has this schedule (`ads_static`); everything else,
+// phx_spec.hip's derive() decides whether an env has this schedule (`ads_static`); everything else,
 // tracking, host-injected messages and dynamic graphs stay on the generic engine, which is also the
 // device-side cross-check of this kernel (tests: fused == generic == oracle).
 #include <cstdlib>
 #include <cstring>
 
 #include "phx_dev.h"
+#include "phx_launch.h"
 
 struct AdsArgs {
   phx_step_io sio;
@@ -68,7 +69,7 @@ __device__ __forceinline__ int ads_count(bool flag, int* red_i) {
 
 // REPLAY (rollouts): recorded actions and / or draws come from HBM (phx_rollout_io.actions / exo).  The device-drawn instantiation has NO
 // global load on a step's common path -- the acting lists' masks are four bits in a register, the publisher's click probabilities sit in LDS,
-// the two stages alternate by the static schedule's premise (phx_api.hip) -- because on gfx950 a load behind the row's stores waits for them
+// the two stages alternate by the static schedule's premise (phx_spec.hip: classify_ads) -- because on gfx950 a load behind the row's stores waits for them
 // (s_waitcnt vmcnt counts both), and a load behind a condition that is never true still leaves its wait at the join.
 template <int NT, bool ROLLOUT, bool REPLAY>
 __global__ __launch_bounds__(NT) void phx_ads_kernel(const DevSpec sp, const AdsArgs args) {
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(NT) void phx_ads_kernel(const DevSpec sp, const Ads
       }
     }
     // ---- FiniteStateMachineEnv epilogue fsm.py:309-380 ---------------------------------------------------
-    const int next_stage = stage == 0 ? 1 : 0;                 // the static schedule's premise: stage_next = {1, 0} (phx_api.hip)
+    const int next_stage = stage == 0 ? 1 : 0;                 // the static schedule's premise: stage_next = {1, 0} (phx_spec.hip: classify_ads)
     uint8_t ov = 0, rv = 0, dv = 0, tm = 0;
     double rw = 0.0;
     float ob[3] = {0.f, 0.f, 0.f};

@@ -120,7 +120,7 @@ struct DevSpec {
   const int32_t* mt_ptr;         // PHX_F_MT19937: [n_lists + 1] / the exogenous indices of a list's drawing agents in acting order
   const int32_t* mt_rank;        //   (the order in which the reference's CustomerAgents call np.random.randint in a step of that list)
   // generic engine, drop-out-free supply-chain specs: the round schedule of a step in which every agent is live and every acting
-  // strategic agent has an action, simulated once at phx_create (phx_api.hip: build_static_schedule).  sched + sched_off[list]:
+  // strategic agent has an action, simulated once at phx_create (phx_spec.hip: build_static_schedule).  sched + sched_off[list]:
   // [R, n_0 .. n_7], act_off[acting items] (queue offset of the item's message or -1), then per round { cnt[A], goff[A], order[n_r],
   // next_off[n_r] } = inbox sizes, inbox offsets in first-arrival (dict) order, the queue index of every inbox position in send
   // order, and where the reply to that position goes in the next queue (-1: none) -- what the acting phase's counts and scan and

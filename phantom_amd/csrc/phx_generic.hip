@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "phx_dev.h"
+#include "phx_launch.h"
 #include "phx_epilogue.h"
 
 #define ERRKEY_NONE 0x7fffffff
@@ -1171,7 +1172,6 @@ __global__ __launch_bounds__(NT, LEAN ? PHX_LEAN_WAVES : ((ROLL && NT == 128 && 
 #undef sp
 #undef g
 
-size_t phx_generic_queue_bytes(int A, int S, int Q, int scan_cap, int n_adx, bool lean);
 #include "phx_generic_sched.hip"      // phx_sched_step_kernel (its tail workgroups call phx_generic_env) and its launcher
 
 // ---- PhantomEnv.reset (env.py:185-237; fsm.py:195-251; stackelberg.py:53-109) -------------------

@@ -3,7 +3,7 @@
 // Round 6.  phx_generic_step_kernel maps one env instance to one wave whose lanes are MESSAGES in the parallel
 // phases and RECEIVERS in the handler phase: at SC64 ten of 64 lanes work while a shop walks its inbox, and every one of the
 // ~15 dependent phases of a step costs its uniform control flow (49 % of the instructions were SALU) once per env.  For a spec
-// whose message flow cannot drop or add a message (phx_api.hip: build_static_schedule -- static Network, supply-chain kinds,
+// whose message flow cannot drop or add a message (phx_spec.hip: build_static_schedule -- static Network, supply-chain kinds,
 // every agent live, every acting shop with an action) the whole flow is known at phx_create: which message sits at which
 // queue position of which round, whose inbox it is in, at which position, and where the reply goes.  This kernel executes
 // that COMPILED schedule:
@@ -27,6 +27,7 @@
 // Reference: env.py:239-336, network.py:233-265, resolvers.py:128-163, agents.py:96-155, supply_chain.py:36-150, fsm.py:253-380.
 // (compiled as part of phx_generic.hip's translation unit: phx_generic_env is defined there)
 #include "phx_dev.h"
+#include "phx_launch.h"
 
 #define sp (*(const DevSpec*)spc)
 #define g (*(const GenArgs*)(kp + 8))

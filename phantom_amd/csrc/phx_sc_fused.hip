@@ -15,7 +15,7 @@
 // shop's inbox -- is staged through LDS from 16-byte coalesced loads of the exo rows.
 // Results are bit-identical to the generic engine (tests/test_gpu_parity.py).
 #include "phx_dev.h"
-#include "phx_sc_fast.h"
+#include "phx_launch.h"
 
 #include <cstdlib>
 #include <cstdio>

@@ -3,7 +3,7 @@
 // phx_policy_mlp (include/phantom_amd.h) and the plain supply chain's (env, shop) row -- its state in registers, the observation it
 // encodes, the customers' orders of a step and the closed form of the step itself.
 #pragma once
-#include "phx_dev.h"
+#include "phx_launch.h"
 
 struct PolArgs {
   int32_t B, S, epb, T, num_steps, n_exo;
@@ -178,5 +178,3 @@ struct PolShop {
     if (s == 0) { a.env_step[b] = step; a.env_tick[b] = (int32_t)tick; }
   }
 };
-
-const char* phx_sc_policy_unsupported(const DevSpec& sp, const phx_rollout_io& io);

@@ -27,7 +27,7 @@
 // phx_sc_rollout_kernel): device RNG and random policy (no replay), every shop with the same 1..6 customers
 // and the same normaliser, whole envs per block with 16-byte aligned tile rows, num_steps >= the chunk length.
 #include "phx_dev.h"
-#include "phx_sc_fast.h"
+#include "phx_launch.h"
 
 #include <cstdio>
 #include <cstdlib>

@@ -17,7 +17,7 @@
 // Draws mask the operands by the position's flags (no action: R = 0, no orders: D = 0), so the recurrence itself is
 // the plain kernel's.  Results are bit-identical to the lane-per-pair loops (tests/test_gpu_round2.py, tests/fuzz_rollouts.py).
 #include "phx_dev.h"
-#include "phx_sc_fast.h"
+#include "phx_launch.h"
 
 #include <atomic>
 #include <cstdio>
@@ -35,7 +35,7 @@ struct FsmFastArgs {
   uint64_t seed; int64_t env_offset;
   int32_t *stock, *sales, *missed, *delivered, *env_step, *env_tick, *env_stage, *env_prev_stage, *env_arrive;
   double* rew_cache; uint8_t* rew_cache_v; float* obs_cache; uint8_t* obs_cache_v;
-  const uint32_t* pos_tab;          // [num_steps] see phx_api.hip: build_fsm_fast
+  const uint32_t* pos_tab;          // [num_steps] see phx_api.hip: plan_fsm_fast
   const int32_t* irregular;         // device word: == gen -> some env is off the tabulated stage chain, this kernel does nothing
   int32_t gen;                      // this launch's number (the check kernel stores it in *irregular: no clearing between launches)
   phx_rollout_io io;

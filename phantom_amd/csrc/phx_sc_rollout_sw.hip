@@ -25,7 +25,7 @@
 // Round 5: fragment lists, several pair groups per workgroup, the REPLAY (MODE 1) and FSM (MODE 2) instantiations, the workers' fused
 // phase, one store piece per trip.
 #include "phx_dev.h"
-#include "phx_sc_fast.h"
+#include "phx_launch.h"
 
 #include <algorithm>
 #include <cstddef>

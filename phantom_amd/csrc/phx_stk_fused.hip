@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "phx_dev.h"
+#include "phx_launch.h"
 
 #define STK_NT 256
 #define STKR_SLOTS 3

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 
-# state-field prefix -> agent kind (phx_api.hip: layout()): what a StageRule's `field` may name
+# state-field prefix -> agent kind (phx_spec.hip: layout()): what a StageRule's `field` may name
 _RULE_FIELD_KIND = {"shop": _abi.KIND_SHOP, "seller": _abi.KIND_SELLER, "buyer": _abi.KIND_BUYER, "cashbox": _abi.KIND_CASHBOX,
                     "reqresp": _abi.KIND_REQRESP, "mock": _abi.KIND_MOCK_STRAT, "adv": _abi.KIND_ADVERTISER, "pub": _abi.KIND_PUBLISHER}
 
@@ -104,7 +104,7 @@ class EnvSpec:
         return int((self.kind == _abi.KIND_CUSTOMER).sum() + pubs.sum() + self.param_i[pubs, 1].sum())
 
     def exo_slot(self) -> np.ndarray:
-        """first exo column of each agent (-1: none), agent order (phx_api.hip derive())."""
+        """first exo column of each agent (-1: none), agent order (phx_spec.hip derive())."""
         out, n = np.full(self.n_agents, -1, dtype=np.int64), 0
         for a in range(self.n_agents):
             k = int(self.kind[a])
