@@ -6,20 +6,44 @@ caller's other torch work and nothing synchronises unless the caller reads value
 There is NO CPU fallback: without a visible GPU or the built HIP library this raises.
 """
 import ctypes as C
+from contextlib import contextmanager
 from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
 from . import _abi
+from ._buffers import AtLeast, Layout, check_tensor
 from .message import Message, payload_to_record, record_to_payload
 from .spec import EnvSpec
-
-_DTYPES = None
 
 
 def _torch():
     import torch
     return torch
+
+
+_ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else None
+# rollout argument-block cache keys: address AND size, so that a buffer freed and reallocated smaller misses
+_sig = lambda x: (x.data_ptr(), x.numel()) if hasattr(x, "data_ptr") else None
+
+
+def _step_layout(B, S, D) -> Layout:
+    """the step outputs: 256-byte aligned sections of ONE device buffer, so that the dict API (PhantomEnv.step) brings
+    them to the host with a single copy (pull_step)"""
+    t = _torch()
+    return Layout([("obs", (B, S, D), t.float32), ("reward", (B, S), t.float64)] +
+                  [(k, (B, S), t.uint8) for k in ("obs_valid", "reward_valid", "terminated", "truncated", "done_valid")] +
+                  [("all_terminated", (B,), t.uint8), ("all_truncated", (B,), t.uint8), ("err", (B,), t.int32)])
+
+
+def _fragment_layout(T, B, S, D, valid_planes: bool, flag_planes: int) -> Layout:
+    """a flat fragment (alloc_trajectory(flat=True)); ``packed_flags``: ``flag_planes`` bit-packed done planes of whole 64-bit words"""
+    t = _torch()
+    step = (T, B, S)
+    masks = [("obs_valid", step, t.uint8), ("reward_valid", step, t.uint8)] if valid_planes else []
+    return Layout([("observations", (T, B, S, D), t.float32), ("actions", step, t.float32), ("rewards", step, t.float32)] + masks +
+                  [("packed_flags", (flag_planes * ((T * B * S + 63) // 64) * 8,), t.uint8),
+                   ("truncations", step, t.uint8), ("terminations", step, t.uint8), ("last_obs", (B, S, D), t.float32)])
 
 
 class StepTensors(NamedTuple):
@@ -68,27 +92,29 @@ class HostStep:
         self._dev, self._buf, self._event, self._seq, self._arrays = dev, buf, event, seq, None
         self._consumed = False          # read_into() has copied the arrays out: nothing is left to keep alive
 
-    def read_into(self, dst: Dict[str, "object"]) -> None:
-        """the arrays copied straight into ``dst`` (same names, shapes and dtypes): one copy instead of get()'s copy + the caller's"""
+    @contextmanager
+    def _host_views(self):
+        """the step's arrays on the host, as views that are valid inside the ``with`` block only (get(): copies that last)"""
         if self._arrays is not None:
-            for k, v in self._arrays.items():
-                np.copyto(dst[k], v)
-            return
-        if self._buf is None:                                     # lazy: from the step outputs themselves
+            yield self._arrays
+        elif self._buf is None:                                   # lazy: from the step outputs themselves
             if self._dev._out_seq != self._seq:
                 raise DeviceError("a poll() result was first read after a later step / reset had overwritten the step outputs: read it "
                                   "before the next send_actions(), or build the adapter with keep_results=True")
-            for k, v in self._dev.pull_step().items():
+            yield self._dev.pull_step()
+        else:
+            if self._dev._host_ring_k - self._seq > 3:            # three pinned buffers rotate: this one has been reused since
+                raise DeviceError("a poll() result was first read more than three steps after it was produced: its host buffer has been reused")
+            self._event.synchronize()
+            yield self._dev._out_layout.numpy_views(self._buf.numpy())
+            if self._dev._host_ring_k - self._seq > 3:            # (reused while it was being read: what the caller took is void)
+                raise DeviceError("a poll() result was read while its host buffer was being reused")
+
+    def read_into(self, dst: Dict[str, "object"]) -> None:
+        """the arrays copied straight into ``dst`` (same names, shapes and dtypes): one copy instead of get()'s copy + the caller's"""
+        with self._host_views() as views:
+            for k, v in views.items():
                 np.copyto(dst[k], v)
-            return
-        if self._dev._host_ring_k - self._seq > 3:
-            raise DeviceError("a poll() result was first read more than three steps after it was produced: its host buffer has been reused")
-        self._event.synchronize()
-        h = self._buf.numpy()
-        for name, shape, dtype, off, n in self._dev._out_layout:
-            np.copyto(dst[name], h[off:off + n].view(np.dtype(str(dtype).replace("torch.", ""))).reshape(shape))
-        if self._dev._host_ring_k - self._seq > 3:
-            raise DeviceError("a poll() result was read while its host buffer was being reused")
         self._consumed = True
 
     def materialise(self) -> None:
@@ -98,21 +124,11 @@ class HostStep:
             self.get()
 
     def get(self) -> Dict[str, "object"]:
-        if self._arrays is None and self._buf is None:            # lazy: the copy is made now, from the step outputs themselves
-            if self._dev._out_seq != self._seq:
-                raise DeviceError("a poll() result was first read after a later step / reset had overwritten the step outputs: read it "
-                                  "before the next send_actions(), or build the adapter with keep_results=True")
-            self._arrays = {k: v.copy() for k, v in self._dev.pull_step().items()}
+        """copies of the arrays, made on the first call and kept (not kept when that read raised)"""
         if self._arrays is None:
-            if self._dev._host_ring_k - self._seq > 3:            # three pinned buffers rotate: this one has been reused since
-                raise DeviceError("a poll() result was first read more than three steps after it was produced: its host buffer has been reused")
-            self._event.synchronize()
-            h = self._buf.numpy()
-            self._arrays = {name: h[off:off + n].view(np.dtype(str(dtype).replace("torch.", ""))).reshape(shape).copy()
-                            for name, shape, dtype, off, n in self._dev._out_layout}
-            if self._dev._host_ring_k - self._seq > 3:            # (reused while it was being read)
-                self._arrays = None
-                raise DeviceError("a poll() result was read while its host buffer was being reused")
+            with self._host_views() as views:
+                arrays = {k: v.copy() for k, v in views.items()}
+            self._arrays = arrays
         return self._arrays
 
 
@@ -177,34 +193,23 @@ class DeviceEnv:
 
         self._kind_rank = spec.kind_rank()
         self._fields: Dict[str, "object"] = {}
-        dt = {0: torch.int32, 1: torch.float64, 2: torch.uint8, 3: torch.float32}
+        dt = {0: torch.int32, 1: torch.float64, 2: torch.uint8, 3: torch.float32}       # phx_field.dtype
         for k in range(self.lib.phx_n_fields(handle)):
             f = _abi.PhxField()
             self.lib.phx_field_info(handle, k, C.byref(f))
             n = f.dim0 * f.dim1 * f.dim2
-            esz = {0: 4, 1: 8, 2: 1, 3: 4}[f.dtype]
-            view = self.state[f.offset:f.offset + n * esz].view(dt[f.dtype])
+            view = self.state[f.offset:f.offset + n * dt[f.dtype].itemsize].view(dt[f.dtype])
             shape = [f.dim0, f.dim1] + ([f.dim2] if f.dim2 > 1 else [])
             self._fields[f.name.decode()] = view.view(*shape)
         B, S, D = self.B, max(self.S, 1), self.D
         z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=self.device)
-        # the step outputs are 256-byte aligned sections of ONE device buffer, so that the dict API
-        # (PhantomEnv.step) brings them to the host with a single copy (pull_step)
-        layout = [("obs", (B, S, D), torch.float32), ("reward", (B, S), torch.float64),
-                  ("obs_valid", (B, S), torch.uint8), ("reward_valid", (B, S), torch.uint8),
-                  ("terminated", (B, S), torch.uint8), ("truncated", (B, S), torch.uint8),
-                  ("done_valid", (B, S), torch.uint8), ("all_terminated", (B,), torch.uint8),
-                  ("all_truncated", (B,), torch.uint8), ("err", (B,), torch.int32)]
-        self._out_layout, total = [], 0
-        for name, shape, dtype in layout:
-            n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-            self._out_layout.append((name, shape, dtype, total, n))
-            total += (n + 255) & ~255
-        self._out_flat = z(total, dtype=torch.uint8)
-        self._out_host = None
+        self._out_layout = _step_layout(B, S, D)
+        self._out_flat = z(self._out_layout.nbytes, dtype=torch.uint8)
+        self._out_host = None                                                # pinned; allocated by the first pull_step()
+        self._host_ring, self._host_ring_owner, self._host_ring_k = [], [None, None, None], 0       # pull_step_async(): ditto
         self._rollout_io_cache = {}
-        for name, shape, dtype, off, n in self._out_layout:
-            setattr(self, name, self._out_flat[off:off + n].view(dtype).view(*shape))
+        for name, view in self._out_layout.torch_views(self._out_flat).items():
+            setattr(self, name, view)
         self.ones_valid = None
         self.msg_log = self.msg_count = None
         if spec.trace_cap > 0:
@@ -277,15 +282,16 @@ class DeviceEnv:
         mp = vp = cp = None
         if conn_on is not None:
             self._conn_on = torch.as_tensor(conn_on, dtype=torch.uint8).to(self.device).contiguous()
-            assert self._conn_on.shape == (self.B, self.spec.n_conn)
+            check_tensor("reset", "conn_on", self._conn_on, torch.uint8, (self.B, self.spec.n_conn), device=self.device)
             cp = self._conn_on.data_ptr()
         if sampler_values is not None:
             self._sampler_values = torch.as_tensor(sampler_values, dtype=torch.float64).to(
                 self.device).contiguous()
-            assert self._sampler_values.shape == (self.B, self.spec.n_samplers)
+            check_tensor("reset", "sampler_values", self._sampler_values, torch.float64, (self.B, self.spec.n_samplers), device=self.device)
             vp = self._sampler_values.data_ptr()
         if mask is not None:
             mask = torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
+            check_tensor("reset", "mask", mask, torch.uint8, (self.B,), device=self.device)
             mp = mask.data_ptr()
             self.err.masked_fill_(mask.bool(), 0)
         else:
@@ -300,26 +306,18 @@ class DeviceEnv:
         """Network.reset() without an env: agent.reset() for every agent."""
         self.reset()
 
-    def _fill_step_io(self, io):
-        io.obs, io.obs_valid = self.obs.data_ptr(), self.obs_valid.data_ptr()
-        io.reward, io.reward_valid = self.reward.data_ptr(), self.reward_valid.data_ptr()
-        io.terminated, io.truncated = self.terminated.data_ptr(), self.truncated.data_ptr()
-        io.done_valid = self.done_valid.data_ptr()
-        io.all_terminated = self.all_terminated.data_ptr()
-        io.all_truncated = self.all_truncated.data_ptr()
-        io.err = self.err.data_ptr()
-        if self.msg_log is not None:
-            io.msg_log, io.msg_count = self.msg_log.data_ptr(), self.msg_count.data_ptr()
-        self._step_io_ref = C.byref(io)
-        self._step_out = StepTensors(self.obs, self.reward, self.terminated, self.truncated,
-                                     self.obs_valid, self.reward_valid, self.done_valid,
-                                     self.all_terminated, self.all_truncated)
-
     def _ensure_step_io(self):
         # the output pointers never change: build the struct once, patch the inputs per call
         if self._step_io is None:
             io = self._step_io = _abi.PhxStepIO()
-            self._fill_step_io(io)
+            for name in self._out_layout.sections:         # (phx_step_io names its outputs as the layout does)
+                setattr(io, name, getattr(self, name).data_ptr())
+            if self.msg_log is not None:
+                io.msg_log, io.msg_count = self.msg_log.data_ptr(), self.msg_count.data_ptr()
+            self._step_io_ref = C.byref(io)
+            self._step_out = StepTensors(self.obs, self.reward, self.terminated, self.truncated,
+                                         self.obs_valid, self.reward_valid, self.done_valid,
+                                         self.all_terminated, self.all_truncated)
         return self._step_io
 
     def step_begin(self, actions, action_valid=None, exo=None, shuffle=None):
@@ -332,18 +330,23 @@ class DeviceEnv:
         step's observations, rewards and done flags (fsm.py:304-380)."""
         torch = _torch()
         io = self._step_io if self._step_io is not None else self._ensure_step_io()
-        if next_stage is not None:
-            if next_stage.dtype != torch.int32 or tuple(next_stage.shape) != (self.B,) or not next_stage.is_contiguous() \
-                    or next_stage.device != self.device:
-                raise ValueError(f"next_stage must be a contiguous int32 tensor [{self.B}] on {self.device}")
-            io.next_stage = next_stage.data_ptr()
-        else:
-            io.next_stage = None
+        io.next_stage = self._next_stage_ptr(next_stage)
         self._out_seq += 1
         rc = self.lib.phx_step_end(self.handle, self._step_io_ref, torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
             self._check(rc, "phx_step_end")
         return self._step_out
+
+    def _input_ptr(self, name, x, dtype, *shape):
+        """the address of an optional per-step input, checked (None: not given)"""
+        if x is None:
+            return None
+        check_tensor("step", name, x, dtype, shape, device=self.device)
+        return x.data_ptr()
+
+    def _next_stage_ptr(self, next_stage):
+        """FSM stage handlers' return values, one stage index per env (None: next_stages[0] / the tabulated handler)"""
+        return self._input_ptr("next_stage", next_stage, _torch().int32, self.B)
 
     def step(self, actions, action_valid=None, exo=None, shuffle=None, next_stage=None, _entry="phx_step") -> StepTensors:
         torch = _torch()
@@ -351,33 +354,16 @@ class DeviceEnv:
         if io is None:
             io = self._ensure_step_io()
         if self.S > 0:
+            # (the once-per-env-step check: the passing case is these comparisons alone, check_tensor states them and raises)
             if actions.dtype != torch.float32 or not actions.is_contiguous() \
                     or actions.shape != (self.B, self.S) or actions.device != self.device:
-                raise ValueError(f"actions must be a contiguous f32 tensor [{self.B}, {self.S}] on {self.device}")
+                check_tensor("step", "actions", actions, torch.float32, (self.B, self.S), device=self.device)
             io.actions = actions.data_ptr()
         io.action_valid = action_valid.data_ptr() if action_valid is not None else None
-        if exo is not None:
-            if exo.dtype != torch.uint8 or exo.shape != (self.B, self.n_exo) or not exo.is_contiguous():
-                raise ValueError(f"exo must be a contiguous u8 tensor [{self.B}, {self.n_exo}]")
-            io.exo = exo.data_ptr()
-        else:
-            io.exo = None
-        if shuffle is not None:                   # recorded np.random.shuffle outcomes (BatchResolver(shuffle_batches=True))
-            if shuffle.dtype != torch.int16 and shuffle.dtype != torch.uint16:
-                raise ValueError("shuffle must be a 16-bit integer tensor")
-            if tuple(shuffle.shape) != (self.B, 8 * self.spec.queue_cap) or not shuffle.is_contiguous() \
-                    or shuffle.device != self.device:
-                raise ValueError(f"shuffle must be a contiguous tensor [{self.B}, {8 * self.spec.queue_cap}] on {self.device}")
-            io.shuffle = shuffle.data_ptr()
-        else:
-            io.shuffle = None
-        if next_stage is not None:                # FSM stage handlers' return values, one stage index per env
-            if next_stage.dtype != torch.int32 or tuple(next_stage.shape) != (self.B,) or not next_stage.is_contiguous() \
-                    or next_stage.device != self.device:
-                raise ValueError(f"next_stage must be a contiguous int32 tensor [{self.B}] on {self.device}")
-            io.next_stage = next_stage.data_ptr()
-        else:
-            io.next_stage = None
+        io.exo = self._input_ptr("exo", exo, torch.uint8, self.B, self.n_exo) if exo is not None else None
+        # recorded np.random.shuffle outcomes (BatchResolver(shuffle_batches=True))
+        io.shuffle = self._input_ptr("shuffle", shuffle, (torch.int16, torch.uint16), self.B, 8 * self.spec.queue_cap) if shuffle is not None else None
+        io.next_stage = self._next_stage_ptr(next_stage) if next_stage is not None else None
         self._out_seq += 1
         rc = getattr(self.lib, _entry)(self.handle, self._step_io_ref,
                                        torch.cuda.current_stream(self.device).cuda_stream)
@@ -392,9 +378,7 @@ class DeviceEnv:
             self._out_host = torch.empty(self._out_flat.shape, dtype=torch.uint8, pin_memory=True)
         self._out_host.copy_(self._out_flat, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
-        h = self._out_host.numpy()
-        return {name: h[off:off + n].view(np.dtype(str(dtype).replace("torch.", ""))).reshape(shape)
-                for name, shape, dtype, off, n in self._out_layout}
+        return self._out_layout.numpy_views(self._out_host.numpy())
 
     def pull_step_lazy(self) -> "HostStep":
         """The last step's outputs, brought to the host only if somebody reads them: ``HostStep.get()`` makes the one device-to-host
@@ -410,11 +394,9 @@ class DeviceEnv:
         nobody kept costs the copy (~25 us of stream time at SC64, B = 4096) and nothing on the host."""
         import weakref
         torch = _torch()
-        ring = self.__dict__.setdefault("_host_ring", [])
-        owners = self.__dict__.setdefault("_host_ring_owner", [None, None, None])
+        ring, owners, k = self._host_ring, self._host_ring_owner, self._host_ring_k
         if len(ring) < 3:
             ring.append(torch.empty(self._out_flat.shape, dtype=torch.uint8, pin_memory=True))
-        k = self.__dict__.get("_host_ring_k", 0)
         slot = k % 3 if len(ring) == 3 else len(ring) - 1
         prev = owners[slot]() if owners[slot] is not None else None
         if prev is not None:
@@ -455,28 +437,12 @@ class DeviceEnv:
         if explore and flat:
             raise ValueError("alloc_trajectory: `explore` planes are not part of a flat fragment")
         if flat:
-            n = T * B * S
-            words = (n + 63) // 64
-            planes = 1 if self.never_terminates() else 2
-            sections = [("observations", (T, B, S, D), torch.float32), ("actions", (T, B, S), torch.float32),
-                        ("rewards", (T, B, S), torch.float32)]
-            if fsm:
-                sections += [("obs_valid", (T, B, S), torch.uint8), ("reward_valid", (T, B, S), torch.uint8)]
-            sections += [("packed_flags", (planes * words * 8,), torch.uint8)]
-            tail = [("truncations", (T, B, S), torch.uint8), ("terminations", (T, B, S), torch.uint8),
-                    ("last_obs", (B, S, D), torch.float32)]
-            offs, total, gather_nbytes = {}, 0, 0
-            for name, shape, dtype in sections + tail:
-                nb = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-                offs[name] = (total, nb, shape, dtype)
-                total += (nb + 255) & ~255
-                if name == "packed_flags":
-                    gather_nbytes = total
-            buf = torch.empty(total, dtype=torch.uint8, device=self.device)
-            v = {k: buf[o:o + nb].view(dt).view(*sh) for k, (o, nb, sh, dt) in offs.items()}
+            layout = _fragment_layout(T, B, S, D, fsm, 1 if self.never_terminates() else 2)
+            buf = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.device)
+            v = layout.torch_views(buf)
             return Trajectory(v["observations"], v["actions"], v["rewards"], v["terminations"], v["truncations"],
                               v["last_obs"], v.get("obs_valid"), v.get("reward_valid"), None, None,
-                              buf, v["packed_flags"], gather_nbytes)
+                              buf, v["packed_flags"], layout.end("packed_flags"))
         # terminations=False: no `terminations` plane (it is all zero for kinds that never terminate; phx_rollout accepts
         # the omission where the serving kernel can leave the plane out and returns an error otherwise)
         # (truncations directly followed by terminations: where the library zero-fills the flag planes before a rollout kernel
@@ -498,62 +464,65 @@ class DeviceEnv:
                              dist_inputs=e(T, B, S, 2, dtype=torch.float32))
         return tr
 
-    def _check_rollout_buffers(self, T, actions, exo, out: Trajectory):
-        """Raw pointers go straight to the kernel: every buffer is checked for dtype, shape,
-        contiguity and device here (python -O strips asserts, so these are real errors)."""
+    def _check_rollout_planes(self, T, out: Trajectory):
+        """the planes of a fragment that receives T steps: at least T rows each, on a 16-byte boundary.  Raw pointers go straight
+        to the kernel, so every buffer is checked here (python -O strips asserts: these are real errors)."""
         torch = _torch()
         B, S, D = self.B, self.S, self.D
 
-        def need(name, x, dtype, tail, lead=None):
-            if x is None:
-                raise ValueError(f"rollout: `{name}` is required for this env")
-            if x.dtype != dtype or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"rollout: `{name}` must be a contiguous {dtype} tensor on {self.device}")
-            if x.data_ptr() % (16 if name.startswith("out.") else x.element_size()):
-                raise ValueError(f"rollout: `{name}` must start on a 16-byte boundary (a view at an odd offset?)")
-            if tuple(x.shape[1:]) != tuple(tail) or (lead is not None and x.shape[0] != lead) \
-                    or (lead is None and x.shape[0] < T):
-                want = (lead if lead is not None else f">={T}",) + tuple(tail)
-                raise ValueError(f"rollout: `{name}` has shape {tuple(x.shape)}, expected {want}")
+        def need(name, dtype, *tail):
+            check_tensor("rollout", "out." + name, getattr(out, name), dtype, (B,) + tail, lead=AtLeast(T), align=16, device=self.device)
 
         if T < 1:
             raise ValueError("rollout: T must be >= 1")
-        if actions is not None:
-            need("actions", actions, torch.float32, (B, S), lead=T)
-        if exo is not None:
-            need("exo", exo, torch.uint8, (B, self.n_exo), lead=T)
-        need("out.observations", out.observations, torch.float32, (B, S, D))
-        need("out.actions", out.actions, torch.float32, (B, S))
-        need("out.rewards", out.rewards, torch.float32, (B, S))
+        need("observations", torch.float32, S, D)
+        need("actions", torch.float32, S)
+        need("rewards", torch.float32, S)
         if out.terminations is not None:                   # None: the all-zero plane left out (the library decides whether it can be)
-            need("out.terminations", out.terminations, torch.uint8, (B, S))
-        need("out.truncations", out.truncations, torch.uint8, (B, S))
-        need("out.last_obs", out.last_obs, torch.float32, (S, D), lead=B)
-        if self._needs_valid_planes():
-            need("out.obs_valid", out.obs_valid, torch.uint8, (B, S))
-            need("out.reward_valid", out.reward_valid, torch.uint8, (B, S))
-        elif out.obs_valid is not None or out.reward_valid is not None:
-            need("out.obs_valid", out.obs_valid, torch.uint8, (B, S))
-            need("out.reward_valid", out.reward_valid, torch.uint8, (B, S))
+            need("terminations", torch.uint8, S)
+        need("truncations", torch.uint8, S)
+        check_tensor("rollout", "out.last_obs", out.last_obs, torch.float32, (B, S, D), align=16, device=self.device)
+        if self._needs_valid_planes() or out.obs_valid is not None or out.reward_valid is not None:
+            need("obs_valid", torch.uint8, S)
+            need("reward_valid", torch.uint8, S)
         if out.msg_log is not None or out.msg_count is not None:
             if self.spec.trace_cap <= 0:
                 raise ValueError("rollout: a message log needs BatchResolver(enable_tracking=True)")
-            need("out.msg_count", out.msg_count, torch.int32, (B,))
-            need("out.msg_log", out.msg_log, torch.uint8, (B, self.spec.trace_cap, 16))
+            need("msg_count", torch.int32)
+            need("msg_log", torch.uint8, self.spec.trace_cap, 16)
 
     def _check_explore_buffers(self, T, noise, out: Trajectory):
-        """an exploring rollout's noise and planes: contiguous f32 on the env's device, [T, B, S] ([T, B, S, 2] for dist_inputs)"""
+        """an exploring rollout's noise and planes (alloc_trajectory(T, explore=True)): [T, B, S] ([T, B, S, 2] for dist_inputs)"""
+        f32, tail = _torch().float32, (self.B, self.S)
+        check_tensor("rollout", "noise", noise, f32, tail, lead=T, device=self.device)
+        check_tensor("rollout", "out.raw_actions", out.raw_actions, f32, tail, lead=AtLeast(T), device=self.device)
+        check_tensor("rollout", "out.action_logp", out.action_logp, f32, tail, lead=AtLeast(T), device=self.device)
+        check_tensor("rollout", "out.dist_inputs", out.dist_inputs, f32, tail + (2,), lead=AtLeast(T), device=self.device)
+
+    def _rollout_io(self, what, T, actions, exo, actions_in_domain, exo_in_domain, last_obs):
+        """the argument block of a T-step phx_rollout: hints, the (checked) replayed inputs, last_obs and err (the planes: _set_planes)"""
         torch = _torch()
-        B, S = self.B, self.S
-        for name, x, shape in (("noise", noise, (T, B, S)), ("out.raw_actions", out.raw_actions, (T, B, S)),
-                               ("out.action_logp", out.action_logp, (T, B, S)), ("out.dist_inputs", out.dist_inputs, (T, B, S, 2))):
-            if x is None:
-                raise ValueError(f"rollout: `{name}` is required with `noise` (alloc_trajectory(T, explore=True))")
-            if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous() or x.data_ptr() % 4:
-                raise ValueError(f"rollout: `{name}` must be a contiguous float32 tensor on {self.device}")
-            lead_ok = x.shape[0] == T if name == "noise" else x.shape[0] >= T
-            if x.dim() != len(shape) or not lead_ok or tuple(x.shape[1:]) != shape[1:]:
-                raise ValueError(f"rollout: `{name}` has shape {tuple(x.shape)}, expected {shape}")
+        if actions is not None:
+            check_tensor(what, "actions", actions, torch.float32, (self.B, self.S), lead=T, device=self.device)
+        if exo is not None:
+            check_tensor(what, "exo", exo, torch.uint8, (self.B, self.n_exo), lead=T, device=self.device)
+        io = _abi.PhxRolloutIO()
+        io.T = T
+        io.hints = (_abi.RH_ACTIONS_IN_DOMAIN if actions_in_domain else 0) | (_abi.RH_EXO_IN_DOMAIN if exo_in_domain else 0)
+        io.actions, io.exo, io.last_obs, io.err = _ptr(actions), _ptr(exo), _ptr(last_obs), self.err.data_ptr()
+        return io
+
+    @staticmethod
+    def _set_planes(dst, o: Trajectory):
+        """a fragment's seven plane pointers into a PhxRolloutIO or a PhxRolloutFrag (the same field names)"""
+        dst.obs, dst.action_out, dst.reward = _ptr(o.observations), _ptr(o.actions), _ptr(o.rewards)
+        dst.terminated, dst.truncated = _ptr(o.terminations), _ptr(o.truncations)
+        dst.obs_valid, dst.reward_valid = _ptr(o.obs_valid), _ptr(o.reward_valid)
+
+    def _cache_put(self, key, entry):
+        if len(self._rollout_io_cache) >= 4:               # tiny LRU: drop the oldest entry
+            self._rollout_io_cache.pop(next(iter(self._rollout_io_cache)))
+        self._rollout_io_cache[key] = entry
 
     def rollout(self, T: int, actions=None, exo=None, out: Optional[Trajectory] = None, actions_in_domain: bool = False,
                 exo_in_domain: bool = False, policy=None, noise=None) -> Trajectory:
@@ -577,23 +546,14 @@ class DeviceEnv:
         # the buffers' addresses and the entry holds no tensor: a fragment allocated here (out=None)
         # is never cached, so repeated env.rollout(T) calls pin nothing (a T=100 SC64 fragment is
         # ~80 MB at B=4096).
-        ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else None
-        sig = lambda x: (x.data_ptr(), x.numel()) if hasattr(x, "data_ptr") else None     # address AND size: a buffer freed
-        key = (T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(sig(x) for x in out[:10]) + (sig(actions), sig(exo), id(policy)) \
-            + ((sig(noise), sig(out.raw_actions), sig(out.action_logp), sig(out.dist_inputs)) if noise is not None else ())   # (and reallocated smaller misses)
+        key = (T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(_sig(x) for x in out[:10]) + (_sig(actions), _sig(exo), id(policy)) \
+            + ((_sig(noise), _sig(out.raw_actions), _sig(out.action_logp), _sig(out.dist_inputs)) if noise is not None else ())
         cached = None if owned else self._rollout_io_cache.get(key)
         if cached is None:
-            self._check_rollout_buffers(T, actions, exo, out)
-            io = _abi.PhxRolloutIO()
-            io.T = T
-            io.hints = (_abi.RH_ACTIONS_IN_DOMAIN if actions_in_domain else 0) | (_abi.RH_EXO_IN_DOMAIN if exo_in_domain else 0)
-            io.actions, io.exo = ptr(actions), ptr(exo)
-            io.obs, io.action_out, io.reward = ptr(out.observations), ptr(out.actions), ptr(out.rewards)
-            io.terminated, io.truncated = ptr(out.terminations), ptr(out.truncations)
-            io.last_obs = ptr(out.last_obs)
-            io.obs_valid, io.reward_valid = ptr(out.obs_valid), ptr(out.reward_valid)
-            io.msg_log, io.msg_count = ptr(out.msg_log), ptr(out.msg_count)
-            io.err = self.err.data_ptr()
+            self._check_rollout_planes(T, out)
+            io = self._rollout_io("rollout", T, actions, exo, actions_in_domain, exo_in_domain, out.last_obs)
+            self._set_planes(io, out)
+            io.msg_log, io.msg_count = _ptr(out.msg_log), _ptr(out.msg_count)
             pol_keep = None
             if policy is not None:
                 if policy.obs_dim != self.D:
@@ -607,12 +567,8 @@ class DeviceEnv:
                     io.reserved_ptr = C.addressof(ex)          # (phx_rollout_io.explore)
             cached = (io, C.byref(io), pol_keep, policy)
             if not owned:
-                if len(self._rollout_io_cache) >= 4:           # tiny LRU: drop the oldest entry
-                    self._rollout_io_cache.pop(next(iter(self._rollout_io_cache)))
-                self._rollout_io_cache[key] = cached
-        rc = self.lib.phx_rollout(self.handle, cached[1], self._stream())        # the library selects its device itself
-        if rc != 0:
-            self._check(rc, "phx_rollout")
+                self._cache_put(key, cached)
+        self._check(self.lib.phx_rollout(self.handle, cached[1], self._stream()), "phx_rollout")     # the library selects its device itself
         return out
 
     def rollout_fragments(self, T: int, outs, actions=None, exo=None, actions_in_domain: bool = False,
@@ -633,41 +589,23 @@ class DeviceEnv:
             return [self.rollout(T, actions, exo, out=outs[0], actions_in_domain=actions_in_domain, exo_in_domain=exo_in_domain)]
         if not 2 <= k <= _abi.MAX_FRAGMENTS:
             raise ValueError(f"rollout_fragments: 1 .. {_abi.MAX_FRAGMENTS} fragments per call, got {k}")
-        ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else None
-        sig = lambda x: (x.data_ptr(), x.numel()) if hasattr(x, "data_ptr") else None
-        key = ("frags", T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(sig(x) for o in outs for x in o[:8]) + (sig(actions), sig(exo))
+        key = ("frags", T, bool(actions_in_domain), bool(exo_in_domain)) + tuple(_sig(x) for o in outs for x in o[:8]) + (_sig(actions), _sig(exo))
         cached = self._rollout_io_cache.get(key)
         if cached is None:
             for o in outs:
                 if o.msg_log is not None:
                     raise ValueError("rollout_fragments: plane fragments without message logs (alloc_trajectory(T))")
-                self._check_rollout_buffers(T, None, None, o)
+                self._check_rollout_planes(T, o)
             if any((o.terminations is None) != (outs[0].terminations is None) for o in outs):
                 raise ValueError("rollout_fragments: `terminations` must be present in every fragment or in none")
-            torch = _torch()
-            for name, x, tail in (("actions", actions, (self.B, self.S)), ("exo", exo, (self.B, self.n_exo))):
-                if x is not None and (tuple(x.shape) != (k * T,) + tail or not x.is_contiguous() or x.device != self.device
-                                      or x.dtype != (torch.float32 if name == "actions" else torch.uint8)):
-                    raise ValueError(f"rollout_fragments: `{name}` must be a contiguous [{k * T}, {tail[0]}, {tail[1]}] tensor on {self.device}")
             arr = (_abi.PhxRolloutFrag * k)()
             for i, o in enumerate(outs):
-                arr[i].obs, arr[i].action_out, arr[i].reward = ptr(o.observations), ptr(o.actions), ptr(o.rewards)
-                arr[i].terminated, arr[i].truncated = ptr(o.terminations), ptr(o.truncations)
-                arr[i].obs_valid, arr[i].reward_valid = ptr(o.obs_valid), ptr(o.reward_valid)
-            io = _abi.PhxRolloutIO()
-            io.T, io.n_frag = k * T, k
-            io.hints = (_abi.RH_ACTIONS_IN_DOMAIN if actions_in_domain else 0) | (_abi.RH_EXO_IN_DOMAIN if exo_in_domain else 0)
-            io.frags = C.cast(arr, C.c_void_p)
-            io.actions, io.exo = ptr(actions), ptr(exo)
-            io.last_obs = ptr(outs[-1].last_obs)
-            io.err = self.err.data_ptr()
+                self._set_planes(arr[i], o)
+            io = self._rollout_io("rollout_fragments", k * T, actions, exo, actions_in_domain, exo_in_domain, outs[-1].last_obs)
+            io.n_frag, io.frags = k, C.cast(arr, C.c_void_p)
             cached = (io, C.byref(io), arr, [o._replace(last_obs=None) for o in outs[:-1]] + [outs[-1]])
-            if len(self._rollout_io_cache) >= 4:
-                self._rollout_io_cache.pop(next(iter(self._rollout_io_cache)))
-            self._rollout_io_cache[key] = cached
-        rc = self.lib.phx_rollout(self.handle, cached[1], self._stream())
-        if rc != 0:
-            self._check(rc, "phx_rollout")
+            self._cache_put(key, cached)
+        self._check(self.lib.phx_rollout(self.handle, cached[1], self._stream()), "phx_rollout")
         return cached[3]
 
     # ---- per-env legacy-numpy MT19937 streams (ABI 7, PHX_F_MT19937) -------------------------------------------------
@@ -684,8 +622,8 @@ class DeviceEnv:
         torch = _torch()
         if out is None:
             out = torch.empty((T, self.B, self.n_exo), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (T, self.B, self.n_exo) or not out.is_contiguous():
-            raise ValueError("mt_draw: `out` must be a contiguous u8 [T, B, n_exo] tensor on the env's device")
+        else:
+            check_tensor("mt_draw", "out", out, torch.uint8, (T, self.B, self.n_exo), device=self.device)
         self._check(self.lib.phx_mt_draw(self.handle, out.data_ptr(), int(T), self._stream()), "phx_mt_draw")
         return out
 
@@ -731,9 +669,7 @@ class DeviceEnv:
             raise ValueError("step_graph needs an actions tensor [n, B, S] or a policy callable")
         if actions is not None:
             n = actions.shape[0] if n is None else n
-            if actions.dtype != torch.float32 or tuple(actions.shape) != (n, self.B, self.S) \
-                    or not actions.is_contiguous() or actions.device != self.device:
-                raise ValueError(f"actions must be a contiguous f32 tensor [{n}, {self.B}, {self.S}] on {self.device}")
+            check_tensor("step_graph", "actions", actions, torch.float32, (n, self.B, self.S), device=self.device)
         elif n is None:
             raise ValueError("step_graph(policy=...) needs n")
         self._ensure_step_io()
@@ -757,7 +693,7 @@ class DeviceEnv:
         if not trajectories:
             raise ValueError("rollout_graph needs at least one trajectory buffer")
         for tr in trajectories:
-            self._check_rollout_buffers(T, None, None, tr)
+            self._check_rollout_planes(T, tr)
         g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream(self.device)
         torch.cuda.synchronize(self.device)
         with torch.cuda.graph(g, stream=side):          # stream capture records the launches, it does not run them

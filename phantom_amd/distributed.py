@@ -11,6 +11,8 @@ the CPU tests.
 """
 from typing import NamedTuple, Optional, Tuple
 
+from ._buffers import Layout
+
 
 class Shard(NamedTuple):
     rank: int
@@ -126,22 +128,17 @@ def all_gather_trajectory(traj, group=None, out=None, staging: str = "auto"):
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     fields = [x.contiguous() for x in traj if x is not None]
-    offs, total = [], 0
-    for x in fields:
-        offs.append(total)
-        total += (x.numel() * x.element_size() + 255) & ~255
-    dev = fields[0].device
+    layout = Layout([(i, x.shape, x.dtype) for i, x in enumerate(fields)])
+    total, dev = layout.nbytes, fields[0].device
     send = torch.empty(total, dtype=torch.uint8, device=dev)
-    for o, x in zip(offs, fields):
-        send[o:o + x.numel() * x.element_size()].copy_(x.view(-1).view(torch.uint8), non_blocking=True)
+    for section, x in zip(layout.torch_views(send).values(), fields):
+        section.copy_(x, non_blocking=True)
     if out is None:
         out = torch.empty((world, total), dtype=torch.uint8, device=dev)
     elif tuple(out.shape) != (world, total) or out.dtype != torch.uint8:
         raise ValueError(f"all_gather_trajectory: out must be a uint8 tensor [{world}, {total}]")
     all_gather_bytes(out, send, group=group, staging=staging)
-    views = tuple(out[:, o:o + x.numel() * x.element_size()].view(x.dtype).view((world,) + tuple(x.shape))
-                  for o, x in zip(offs, fields))
-    return GatheredFields(views, out)
+    return GatheredFields(tuple(layout.torch_views(out).values()), out)
 
 
 class GatheredFields(tuple):
@@ -189,28 +186,17 @@ class RolloutCollector:
         self.device = like[0].device
         # every field of a chunk lives in ONE flat staging buffer (256-byte aligned sections), so a
         # chunk is a single all_gather_into_tensor whatever the number of trajectory arrays
-        shapes = [(chunk,) + tuple(x.shape[1:]) for x in like]
-        nbytes = [int(torch.tensor(sh).prod()) * x.element_size() for sh, x in zip(shapes, like)]
-        offs, total = [], 0
+        sections = [(i, (chunk,) + tuple(x.shape[1:]), x.dtype) for i, x in enumerate(like)]
         n_gathered = len(like) if n_gathered is None else n_gathered
         self.before_gather, self.payload = before_gather, payload
         self.staging, self._stage = staging, None
-        for k, n in enumerate(nbytes):
-            offs.append(total)
-            total += (n + 255) & ~255
-            if k == n_gathered - 1:
-                self.nbytes = total                      # what one chunk sends per rank
-        staging_total = total
-
-        def views(flat, lead):
-            # flat: uint8 [..., total] -> one typed view [..., chunk, B_local, ...] per field
-            return tuple(flat[..., o:o + n].view(x.dtype).unflatten(-1, sh)
-                         for o, n, sh, x in zip(offs, nbytes, shapes, like) if o + n <= flat.shape[-1])
-
-        self._flat = [torch.empty(staging_total, dtype=torch.uint8, device=self.device) for _ in range(n_buffers)]
-        self.bufs = [views(f, ()) for f in self._flat]
+        staged, sent = Layout(sections), Layout(sections[:n_gathered])      # (sent: a prefix of staged, at the same offsets)
+        self.nbytes = sent.nbytes                        # what one chunk sends per rank
+        # one typed view [..., chunk, B_local, ...] per field
+        self._flat = [torch.empty(staged.nbytes, dtype=torch.uint8, device=self.device) for _ in range(n_buffers)]
+        self.bufs = [tuple(staged.torch_views(f).values()) for f in self._flat]
         self._out_flat = torch.empty((self.n_chunks, self.world, self.nbytes), dtype=torch.uint8, device=self.device)
-        self.out = views(self._out_flat, (self.n_chunks, self.world))[:n_gathered]
+        self.out = tuple(sent.torch_views(self._out_flat).values())
         self.cuda = self.device.type == "cuda"
         if self.cuda:
             self.side = torch.cuda.Stream(self.device)
