@@ -75,3 +75,15 @@ bufs = [dev.alloc_trajectory(100) for _ in range(4)]
 dev.rollout_fragments(100, bufs)
 print("FSM fragment list: 4 x", tuple(bufs[0].observations.shape), "from", dev.last_kernel().split("+")[0],
       "| shops observe on", int(bufs[0].obs_valid[:, 0, 0].sum()), "of 100 steps, rewards emitted on", int((bufs[0].reward_valid[:, 0, 0] == 1).sum()))
+
+# 8. a PPO learner's batch: an exploring device policy collects T steps, a torch critic scores them, and ONE launch (phx_gae) turns
+#    rewards, done flags and value predictions into advantages and value targets -- RLlib's compute_advantages on the device
+env = ph.SupplyChainEnv(n_shops=9, customers_per_shop=6, batch_size=4096, seed=42, exogenous="device")
+env.reset()
+rng = np.random.default_rng(0)
+pol = ph.MLPPolicy([rng.normal(0, 0.5, (32, 3)).astype(np.float32), rng.normal(0, 0.2, (2, 32)).astype(np.float32)],
+                   [np.zeros(32, np.float32), np.array([0.0, -0.5], np.float32)], out_scale=60.0, out_bias=45.0)     # (mean, log_std) head
+critic = torch.nn.Sequential(torch.nn.Linear(3, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(env._device().device)
+batch = env.sample(100, policy=pol, explore=True, value_fn=critic, gamma=0.99, lambda_=0.95)
+cols = batch.to_sample_batches()["default_policy"]
+print("PPO batch:", cols["advantages"].shape[0], "rows from", env._device().last_kernel(), "| columns", sorted(cols))

@@ -130,6 +130,13 @@ class PhxRolloutFrag(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("obs", "action_out", "reward", "terminated", "truncated", "obs_valid", "reward_valid")]
 
 
+class PhxGaeIO(C.Structure):
+    """phx_gae_io (include/phantom_amd_gae.h): the planes of one phx_gae call"""
+    _fields_ = [("T", C.c_int32), ("reserved0", C.c_int32), ("N", C.c_int64), ("gamma", C.c_float), ("lambda_", C.c_float)] + [
+        (n, C.c_void_p) for n in ("reward", "vf_pred", "vf_next", "terminated", "truncated", "advantage", "value_target")]
+
+
+GAE_KERNEL = "phx_gae_kernel"
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -224,6 +231,14 @@ def bind_signatures(lib):
     return lib
 
 
+def bind_gae(lib):
+    """restype / argtypes of include/phantom_amd_gae.h's entry point: libphantom_amd.so only (the CPU restatement behind
+    phantom_amd.h's symbols has no such function, so this is not part of bind_signatures)"""
+    lib.phx_gae.restype = C.c_int32
+    lib.phx_gae.argtypes = [C.POINTER(PhxGaeIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -239,6 +254,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     bind_signatures(lib)
+    bind_gae(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -394,7 +394,8 @@ static int bind_blob_and_reset(const phx_spec* spec, const Derived& der, phx_env
 }
 
 static thread_local char g_kernels[384] = "";
-static void note_reset() { g_kernels[0] = 0; }
+void phx_note_reset() { g_kernels[0] = 0; }
+static void note_reset() { phx_note_reset(); }
 void phx_note_kernel(const char* name) {
   const size_t n = strlen(g_kernels), m = strlen(name);
   if (strstr(g_kernels, name) || n + m + 2 >= sizeof g_kernels) return;

@@ -224,6 +224,7 @@ inline int phx_device_cu_count() {
 
 // names of the kernels the calling thread's last phx_step / phx_rollout / phx_resolve launched (phx_last_kernel, tests)
 void phx_note_kernel(const char* name);
+void phx_note_reset();      // a call that is no step / rollout / resolve starts its own list (phx_gae)
 
 struct GenArgs {               // arguments of the generic engine kernel
   phx_step_io io;

@@ -1,0 +1,125 @@
+// phx_gae.hip -- phx_gae (include/phantom_amd_gae.h): advantages and value targets of a rollout fragment in one launch.
+//
+// The recurrence runs backwards over the T rows of a column and is two fmaf and two adds per element: the kernel streams
+// its planes once and is bound by memory, within a column by load latency.  No load depends on the chain, so:
+//   * a lane owns ONE column and a wave 64 consecutive ones: every row access of a wave is one coalesced 256-byte (f32) or
+//     64-byte (u8) piece, at any alignment of the input planes and for any N (lanes past N leave at entry).  One wave per
+//     workgroup, so that the 576 waves of N = 36 864 spread over the chip's 1 024 SIMDs;
+//   * with less than a wave per SIMD, the bytes in flight come from depth: the loads of GAE_K rows are issued a chunk ahead
+//     into the second of two register buffers, then the chain of the current chunk runs, then its stores.  Loads and stores
+//     share vmcnt on gfx950: the next chunk's loads are issued BEFORE this chunk's stores, and no load sits
+//     behind a branch -- rows past the fragment's first are clamped to row 0 (loaded again, never used);
+//   * vf_next is loaded with the chunk, unconditionally: a select, not arithmetic, discards the rows the definition does
+//     not read (what was measured against loading only the rows a wave's ballot asks for: DESIGN 3.4e);
+//   * the outputs are never read again: non-temporal stores, as the store-wave rollout kernel's.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/phantom_amd_gae.h"
+#include "phx_spec.h"
+
+constexpr int GAE_K = 16;          // rows per chunk (tests/test_gpu_gae.py walks T below, at and across it)
+constexpr int GAE_LANES = 64;      // columns per workgroup: one wave
+
+template <bool HAS_V, bool HAS_NEXT, bool HAS_TERM>
+struct GaeChunk {
+  float r[GAE_K], v[HAS_V ? GAE_K : 1], vn[HAS_NEXT ? GAE_K : 1];
+  uint32_t tr[GAE_K], te[HAS_TERM ? GAE_K : 1];
+};
+
+// rows t_hi, t_hi - 1 .. t_hi - GAE_K + 1 of column n (rows below 0: row 0 again)
+template <bool HAS_V, bool HAS_NEXT, bool HAS_TERM>
+__device__ __forceinline__ void gae_load(GaeChunk<HAS_V, HAS_NEXT, HAS_TERM>& c, const phx_gae_io& a, const int64_t n, const int t_hi) {
+#pragma unroll
+  for (int k = 0; k < GAE_K; ++k) {
+    const int t = t_hi - k > 0 ? t_hi - k : 0;
+    const int64_t o = (int64_t)t * a.N + n;
+    c.r[k] = a.reward[o];
+    if (HAS_V) c.v[k] = a.vf_pred[o];
+    if (HAS_NEXT) c.vn[k] = a.vf_next[o];
+    c.tr[k] = a.truncated[o];
+    if (HAS_TERM) c.te[k] = a.terminated[o];
+  }
+}
+
+// the definition for the chunk's rows that exist; adv_next / v_next: advantage[t + 1][n] and vf_pred[t + 1][n] on entry and exit
+template <bool HAS_V, bool HAS_NEXT, bool HAS_TERM>
+__device__ __forceinline__ void gae_chain(const GaeChunk<HAS_V, HAS_NEXT, HAS_TERM>& c, const phx_gae_io& a, const float gl, const int64_t n,
+                                          const int t_hi, float& adv_next, float& v_next) {
+#pragma unroll
+  for (int k = 0; k < GAE_K; ++k) {
+    const int t = t_hi - k;
+    if (t < 0) break;                                    // (wave-uniform, and around stores only)
+    const int64_t o = (int64_t)t * a.N + n;
+    const bool term = HAS_TERM && c.te[k] != 0;
+    const bool cut = term || c.tr[k] != 0 || t == a.T - 1;
+    const float v = HAS_V ? c.v[k] : 0.0f;
+    const float nv = term ? 0.0f : (cut ? (HAS_NEXT ? c.vn[k] : 0.0f) : v_next);
+    const float cc = cut ? 0.0f : adv_next;
+    const float d = __builtin_fmaf(a.gamma, nv, c.r[k]) - v;
+    const float adv = __builtin_fmaf(gl, cc, d);
+    __builtin_nontemporal_store(adv, a.advantage + o);
+    if (a.value_target) __builtin_nontemporal_store(adv + v, a.value_target + o);
+    adv_next = adv;
+    v_next = v;
+  }
+}
+
+template <bool HAS_V, bool HAS_NEXT, bool HAS_TERM>
+__global__ __launch_bounds__(GAE_LANES) void phx_gae_kernel(const phx_gae_io a, const float gl) {
+  const int64_t n = (int64_t)blockIdx.x * GAE_LANES + threadIdx.x;
+  if (n >= a.N) return;
+  GaeChunk<HAS_V, HAS_NEXT, HAS_TERM> c0, c1;
+  float adv_next = 0.0f, v_next = 0.0f;                  // (never used at t == T - 1: the row is a cut)
+  int t_hi = a.T - 1;
+  gae_load(c0, a, n, t_hi);
+  for (;;) {
+    gae_load(c1, a, n, t_hi - GAE_K);
+    gae_chain(c0, a, gl, n, t_hi, adv_next, v_next);
+    t_hi -= GAE_K;
+    if (t_hi < 0) break;
+    gae_load(c0, a, n, t_hi - GAE_K);
+    gae_chain(c1, a, gl, n, t_hi, adv_next, v_next);
+    t_hi -= GAE_K;
+    if (t_hi < 0) break;
+  }
+}
+
+template <bool HAS_V, bool HAS_NEXT, bool HAS_TERM>
+static void gae_launch(const phx_gae_io& io, const float gl, hipStream_t st) {
+  const unsigned grid = (unsigned)((io.N + GAE_LANES - 1) / GAE_LANES);
+  hipLaunchKernelGGL((phx_gae_kernel<HAS_V, HAS_NEXT, HAS_TERM>), dim3(grid), dim3(GAE_LANES), 0, st, io, gl);
+}
+
+extern "C" int phx_gae(const phx_gae_io* io, void* stream) {
+  if (!io) return fail(PHX_EINVAL, "phx_gae: null io");
+  if (io->reserved0 != 0) return fail(PHX_EINVAL, "phx_gae: reserved0 must be 0");
+  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_gae: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
+  if (io->N > (int64_t)GAE_LANES * 0x7fffffff) return fail(PHX_EINVAL, "phx_gae: N = %lld is beyond one launch's grid", (long long)io->N);
+  if (!(io->gamma >= 0.0f && io->gamma <= 1.0f) || !(io->lambda >= 0.0f && io->lambda <= 1.0f))
+    return fail(PHX_EINVAL, "phx_gae: gamma = %g and lambda = %g must lie in [0, 1]", (double)io->gamma, (double)io->lambda);
+  if (!io->reward || !io->truncated || !io->advantage) return fail(PHX_EINVAL, "phx_gae: reward, truncated and advantage are required");
+  if (((uintptr_t)io->reward | (uintptr_t)io->vf_pred | (uintptr_t)io->vf_next) & 3u)
+    return fail(PHX_EINVAL, "phx_gae: reward, vf_pred and vf_next must be 4-byte aligned");
+  if (((uintptr_t)io->advantage | (uintptr_t)io->value_target) & 15u)
+    return fail(PHX_EINVAL, "phx_gae: advantage and value_target must be 16-byte aligned");
+  const float gl = io->gamma * io->lambda;               // one f32 multiply (the build has -ffp-contract=off)
+  const hipStream_t st = (hipStream_t)stream;
+  const int which = (io->vf_pred ? 4 : 0) | (io->vf_next ? 2 : 0) | (io->terminated ? 1 : 0);
+  switch (which) {
+    case 0: gae_launch<false, false, false>(*io, gl, st); break;
+    case 1: gae_launch<false, false, true>(*io, gl, st); break;
+    case 2: gae_launch<false, true, false>(*io, gl, st); break;
+    case 3: gae_launch<false, true, true>(*io, gl, st); break;
+    case 4: gae_launch<true, false, false>(*io, gl, st); break;
+    case 5: gae_launch<true, false, true>(*io, gl, st); break;
+    case 6: gae_launch<true, true, false>(*io, gl, st); break;
+    default: gae_launch<true, true, true>(*io, gl, st); break;
+  }
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return fail(PHX_EHIP, "phx_gae: %s", hipGetErrorString(he));
+  phx_note_reset();
+  phx_note_kernel("phx_gae_kernel");
+  return PHX_OK;
+}

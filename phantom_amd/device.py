@@ -655,6 +655,42 @@ class DeviceEnv:
                     "phx_unpack_flags")
         return out
 
+    def gae(self, rewards, truncations, vf_pred=None, vf_next=None, terminations=None, gamma: float = 0.99,
+            lambda_: float = 1.0, out=None):
+        """``(advantages, value_targets)`` of a time-major fragment in ONE launch on the current stream (phx_gae,
+        include/phantom_amd_gae.h): RLlib's ``compute_advantages(use_gae=True)`` for every (env instance, agent) column at
+        once.  All tensors are ``[T, B, S]`` (or ``[T, N]``) on the env's device: ``rewards`` f32 and ``truncations`` u8 as a
+        rollout wrote them (slices of longer recordings are fine), ``vf_pred`` f32 = V(the observation the policy acted on),
+        ``vf_next`` f32 = V(new_obs[t]), read only where a trajectory is cut without terminating (a truncation, the fragment's
+        last row), ``terminations`` u8; a missing value plane reads as 0 (``vf_pred=None, lambda_=1``: discounted returns), a
+        missing ``terminations`` as all zero.  ``out``: the two f32 result tensors, 16-byte aligned (allocated here when None).
+        Plain envs: there are no validity planes (FSM / Stackelberg dicts omit keys)."""
+        torch = _torch()
+        f32, u8 = torch.float32, torch.uint8
+        if rewards is None or rewards.dim() < 2:
+            raise ValueError("gae: `rewards` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(rewards.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"gae: `rewards` has shape {shape}: T and N must be >= 1")
+        if not (0.0 <= gamma <= 1.0 and 0.0 <= lambda_ <= 1.0):
+            raise ValueError(f"gae: gamma = {gamma} and lambda_ = {lambda_} must lie in [0, 1]")
+        check_tensor("gae", "rewards", rewards, f32, shape, device=self.device)
+        check_tensor("gae", "truncations", truncations, u8, shape, device=self.device)
+        for name, x, dtype in (("vf_pred", vf_pred, f32), ("vf_next", vf_next, f32), ("terminations", terminations, u8)):
+            if x is not None:
+                check_tensor("gae", name, x, dtype, shape, device=self.device)
+        if out is None:
+            out = (torch.empty(shape, dtype=f32, device=self.device), torch.empty(shape, dtype=f32, device=self.device))
+        adv, vt = out
+        check_tensor("gae", "out[0]", adv, f32, shape, align=16, device=self.device)
+        check_tensor("gae", "out[1]", vt, f32, shape, align=16, device=self.device)
+        io = _abi.PhxGaeIO(T=T, N=N, gamma=gamma, lambda_=lambda_, reward=_ptr(rewards), vf_pred=_ptr(vf_pred), vf_next=_ptr(vf_next),
+                           terminated=_ptr(terminations), truncated=_ptr(truncations), advantage=_ptr(adv), value_target=_ptr(vt))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_gae(C.byref(io), self._stream()), "phx_gae")
+        return adv, vt
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

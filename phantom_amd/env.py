@@ -418,7 +418,8 @@ class PhantomEnv:
         self._obs_state = ("traj", traj.last_obs)               # what the strategic agents observe now (sample() starts from it)
         return traj
 
-    def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None):
+    def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
+               gamma: float = 0.99, lambda_: float = 1.0):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -431,7 +432,13 @@ class PhantomEnv:
         ``policy``: an ``MLPPolicy`` evaluated on the device (on-policy sampling, plain supply chains); ``explore=True`` samples its
         Gaussian (a stochastic policy) with noise from ``torch.randn(generator=generator)`` -- without a generator the env's own, seeded
         from (seed, env_offset), so that shards draw independently -- and the batch carries ``raw_actions`` / ``action_logp`` /
-        ``dist_inputs`` (RLlib's actions, action_logp, action_prob and action_dist_inputs columns)."""
+        ``dist_inputs`` (RLlib's actions, action_logp, action_prob and action_dist_inputs columns).
+
+        ``value_fn``: the critic, a callable (an ``nn.Module`` works) from a device tensor f32 [M, D] to f32 [M] or [M, 1].  It is
+        called once on every row's ``obs`` and once on ``new_obs`` of the rows where a trajectory can be cut (each piece's last row:
+        an episode's end or the fragment's); one ``DeviceEnv.gae`` launch then turns rewards, done flags and the two value planes
+        into generalised advantage estimates with ``gamma`` / ``lambda_`` (RLlib's ``compute_advantages``), and the batch carries
+        ``vf_preds`` / ``advantages`` / ``value_targets``.  Without ``value_fn`` nothing of this runs."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -461,7 +468,7 @@ class PhantomEnv:
             noise = torch.randn((T, B, S), generator=gen, dtype=torch.float32, device=dev.device)
             raw, logp = torch.empty_like(act), torch.empty_like(act)
             dist = torch.empty((T, B, S, 2), dtype=torch.float32, device=dev.device)
-        done, ep = 0, ep0
+        done, ep, piece_ends = 0, ep0, []
         while done < T:
             n = min(T - done, N - cur)
             # (a slice of the caller's tensor may start off a 16-byte boundary -- B * S * 4 or B * n_exo not a multiple of 16: fine since
@@ -480,19 +487,34 @@ class PhantomEnv:
             if cur == N:
                 cur, ep = 0, ep + 1
             done += n
+            piece_ends.append(done - 1)
         self._episodes_done = ep
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device
         cols = {"obs": am(obs), "new_obs": am(new_obs), "actions": am(act), "rewards": am(rew), "terminateds": am(term),
                 "truncateds": am(trunc)}
         if explore:
             cols.update(raw_actions=am(raw), action_logp=am(logp), dist_inputs=am(dist))
+        if value_fn is not None:
+            def values(x):                                                    # f32 [R, B, S, D] -> the critic's f32 [R, B, S]
+                v = value_fn(x.reshape(-1, D))
+                if v.dtype != torch.float32 or v.numel() != x.shape[0] * B * S:
+                    raise ValueError(f"sample: `value_fn` must map f32 [M, {D}] to f32 [M] or [M, 1], got {v.dtype} {tuple(v.shape)}")
+                return v.detach().reshape(x.shape[0], B, S).contiguous()
+            with torch.no_grad():
+                vf = values(obs)
+                ends = torch.as_tensor(piece_ends, device=dev.device)
+                vf_next = torch.zeros_like(vf)
+                vf_next[ends] = values(new_obs[ends])
+            adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
+            cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         return FragmentBatch(ids, host["obs"], host["new_obs"], host["actions"], host["rewards"], host["terminateds"].astype(bool),
                              host["truncateds"].astype(bool), np.broadcast_to(t_in_ep, (B, T)).copy(),
                              (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64),
                              never_finishes_alone=dev.never_terminates(), raw_actions=host.get("raw_actions"),
-                             action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"))
+                             action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"), vf_preds=host.get("vf_preds"),
+                             advantages=host.get("advantages"), value_targets=host.get("value_targets"))
 
     def _noise_generator(self, device):
         """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""

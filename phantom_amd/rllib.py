@@ -408,12 +408,15 @@ class BatchedBaseEnv(_BaseEnvBase):
             dev.close()
             self.env._dev = None                                   # a later call (try_restart / try_reset after stop) rebuilds the device env
 
-    def sample(self, T: int, actions=None, exo=None, policy_mapping_fn=None, policy=None, explore: bool = False, generator=None):
+    def sample(self, T: int, actions=None, exo=None, policy_mapping_fn=None, policy=None, explore: bool = False, generator=None,
+               value_fn=None, gamma: float = 0.99, lambda_: float = 1.0):
         """The bulk exit: T steps of every env instance in fused device rollouts and the fragment as per-policy ``SampleBatch``
         column dicts (phantom_amd.rollout.FragmentBatch.to_sample_batches) -- no python object per (env, agent, step).
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
-        ``generator``: on-policy sampling with a device policy, deterministic or exploring (PhantomEnv.sample)."""
-        return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator).to_sample_batches(policy_mapping_fn)
+        ``generator``: on-policy sampling with a device policy, deterministic or exploring; ``value_fn`` / ``gamma`` / ``lambda_``: a critic, for the
+        ``vf_preds`` / ``advantages`` / ``value_targets`` columns (PhantomEnv.sample)."""
+        return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
+                               lambda_=lambda_).to_sample_batches(policy_mapping_fn)
 
     def try_restart(self, env_id: Optional[int] = None) -> None:
         """RLlib calls this after a sub-env fault; the device env has no per-instance process to restart: reset it."""

@@ -165,6 +165,8 @@ class FragmentBatch:
     an exploring policy's fragment (PhantomEnv.sample(explore=True)), else None:
     ``raw_actions`` f32 [B, S, T] the Gaussian draw z (``actions`` stays what the env took: clip(out_scale z + out_bias))
     ``action_logp`` f32 [B, S, T] log N(z; mean, exp(log_std))              ``dist_inputs`` f32 [B, S, T, 2] (mean, log_std)
+    a fragment sampled with a critic (PhantomEnv.sample(value_fn=...)), else None -- RLlib's columns of the same names:
+    ``vf_preds`` f32 [B, S, T] V(obs)       ``advantages`` / ``value_targets`` f32 [B, S, T] (DeviceEnv.gae)
     """
 
     COLUMNS = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
@@ -172,7 +174,7 @@ class FragmentBatch:
     def __init__(self, agent_ids, obs, new_obs, actions, rewards, terminateds, truncateds, t, eps_id,
                  obs_valid=None, new_obs_valid=None, reward_valid=None, stage=None, stage_ids=None,
                  action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
-                 dist_inputs=None):
+                 dist_inputs=None, vf_preds=None, advantages=None, value_targets=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -182,6 +184,7 @@ class FragmentBatch:
         self.action_shape = tuple(action_shape)
         self.never_finishes_alone = never_finishes_alone
         self.raw_actions, self.action_logp, self.dist_inputs = raw_actions, action_logp, dist_inputs
+        self.vf_preds, self.advantages, self.value_targets = vf_preds, advantages, value_targets
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
     # ---- RLlib-shaped exit -------------------------------------------------------------------------------------------
@@ -191,7 +194,8 @@ class FragmentBatch:
         (default: everything under ``"default_policy"``).  Agents of one policy that are consecutive in agent order come
         out as reshaped VIEWS of the host arrays (no copy); envs whose dicts omit keys (FSM / Stackelberg) drop the rows of
         absent observations (boolean mask: a copy).  An exploring fragment's ``actions`` column is the raw draw z (what RLlib's
-        sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``."""
+        sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``; a fragment with
+        ``vf_preds`` / ``advantages`` / ``value_targets`` has the columns of those names."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
         for s, aid in enumerate(self.agent_ids):
@@ -219,6 +223,9 @@ class FragmentBatch:
                 cols["action_logp"] = sel(self.action_logp).reshape(-1)
                 cols["action_prob"] = np.exp(cols["action_logp"])
                 cols["action_dist_inputs"] = sel(self.dist_inputs).reshape(B * n * T, -1)
+            for name in ("vf_preds", "advantages", "value_targets"):
+                if getattr(self, name) is not None:
+                    cols[name] = sel(getattr(self, name)).reshape(-1)
             if self.obs_valid is not None:
                 keep = sel(self.obs_valid).reshape(-1).astype(bool)
                 cols = {k: v[keep] for k, v in cols.items()}

@@ -1,0 +1,144 @@
+"""phx_gae (include/phantom_amd_gae.h) against the torch reverse loop a user would write without it, at SC64's trajectory planes.
+    python tools/gae_time.py [--out profiles/gae_time.txt] [--seconds 0.5] [--repeats 5]
+GPU only: no device, no number.  Per shape the two are timed in ONE process, alternating, `repeats` times each over a window of
+`seconds`, with HIP events; the kernel rotates over buffer sets whose total exceeds 256 MB, so that its planes come from HBM and not
+from the Infinity Cache.  Roofline: the bytes the ALGORITHM needs, from the shapes -- 4 B per element of a value or output plane, 1 B
+per element of a flag plane, a plane counted only when it is given, vf_next counted as the rows the definition reads -- over the
+8 TB/s peak, as bench.py's `roofline` does."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from phantom_amd import _abi
+
+PEAK_BYTES_PER_S = 8e12
+S, EPISODE = 9, 100                                       # SC64: 9 shops; 100-step episodes end in lock-step
+SHAPES = ((4096, 100), (4096, 800), (65536, 100))         # (B, T)
+GAMMA, LAMBDA = 0.99, 0.95
+
+
+def algorithmic_bytes(T, N, cut_rows, vf_pred=True, vf_next=True, terminated=True, value_target=True):
+    """bytes the definition reads and writes: reward + advantage, the planes that are given, vf_next at the rows it is read"""
+    per_elem = 4 + 4 + 1 + (4 if vf_pred else 0) + (1 if terminated else 0) + (4 if value_target else 0)
+    return T * N * per_elem + (4 * cut_rows * N if vf_next else 0)
+
+
+def buffer_set(T, N, dev, gen):
+    f = lambda: torch.randn((T, N), generator=gen, device=dev)
+    trunc = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+    trunc[EPISODE - 1::EPISODE] = 1
+    return dict(reward=f(), vf_pred=f(), vf_next=f(), terminated=torch.zeros_like(trunc), truncated=trunc,
+                advantage=torch.empty((T, N), device=dev), value_target=torch.empty((T, N), device=dev))
+
+
+def gae_io(b, T, N):
+    return _abi.PhxGaeIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, **{k: v.data_ptr() for k, v in b.items()})
+
+
+def torch_loop(b, adv, vt):
+    """the same quantities with element-wise torch ops, one row at a time (what the kernel replaces)"""
+    r, v, vn = b["reward"], b["vf_pred"], b["vf_next"]
+    term, cut = b["terminated"].bool(), (b["terminated"] | b["truncated"]).bool()
+    T = r.shape[0]
+    last = torch.zeros_like(r[0])
+    zero = torch.zeros_like(r[0])
+    for t in range(T - 1, -1, -1):
+        if t == T - 1:
+            nv = torch.where(term[t], zero, vn[t])
+            delta = r[t] + GAMMA * nv - v[t]
+            last = delta
+        else:
+            nv = torch.where(term[t], zero, torch.where(cut[t], vn[t], v[t + 1]))
+            delta = r[t] + GAMMA * nv - v[t]
+            last = delta + (GAMMA * LAMBDA) * torch.where(cut[t], zero, last)
+        adv[t] = last
+    torch.add(adv, v, out=vt)
+
+
+def window(fn, seconds):
+    """microseconds per call of fn(i) over a window of about `seconds` (HIP events around the whole window)"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); fn(0); e1.record(); torch.cuda.synchronize()
+    n = max(3, int(seconds * 1e3 / max(e0.elapsed_time(e1), 1e-3)))
+    e0.record()
+    for i in range(n):
+        fn(i)
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3, n
+
+
+def measure(lib, B, T, seconds, repeats, dev):
+    N = B * S
+    gen = torch.Generator(device=dev).manual_seed(0)
+    one = T * N * 22
+    n_sets = max(2, -(-(256 << 20) // one) + 1)           # working set beyond the 256 MiB Infinity Cache
+    sets = [buffer_set(T, N, dev, gen) for _ in range(n_sets)]
+    ios = [gae_io(b, T, N) for b in sets]
+    refs = [C.byref(io) for io in ios]
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def kernel(i):
+        rc = lib.phx_gae(refs[i % n_sets], stream)
+        if rc != 0:
+            raise RuntimeError(lib.phx_last_error().decode())
+
+    adv_t, vt_t = torch.empty((T, N), device=dev), torch.empty((T, N), device=dev)
+    loop = lambda i: torch_loop(sets[i % n_sets], adv_t, vt_t)
+    kernel(0); loop(0); torch.cuda.synchronize()           # warm-up, and the two agree (f32, different association: a tolerance)
+    err = float((sets[0]["advantage"] - adv_t).abs().max())
+    if not err < 1e-3:
+        raise RuntimeError(f"kernel and torch loop disagree: max |diff| = {err}")
+    for i in range(n_sets):
+        kernel(i)
+    ks, ls = [], []
+    for _ in range(repeats):                              # alternating
+        ks.append(window(kernel, seconds)[0])
+        ls.append(window(loop, seconds)[0])
+    cut_rows = len(range(EPISODE - 1, T, EPISODE)) + (0 if T % EPISODE == 0 else 1)
+    by = algorithmic_bytes(T, N, cut_rows)
+    return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, bytes=by, kernel_us=ks, loop_us=ls, max_abs_diff=err)
+
+
+def report(rows):
+    out = ["phx_gae_kernel against the torch reverse loop (tools/gae_time.py); SC64 planes, N = 9 B columns, episodes of 100 steps,",
+           f"gamma = {GAMMA}, lambda = {LAMBDA}, every plane given.  Times: median [min .. max] over the repeats, microseconds per call.",
+           f"device: {torch.cuda.get_device_name()}", ""]
+    ok = True
+    for r in rows:
+        k, l = np.array(r["kernel_us"]), np.array(r["loop_us"])
+        km, lm = float(np.median(k)), float(np.median(l))
+        share = r["bytes"] / (km * 1e-6) / PEAK_BYTES_PER_S
+        faster = bool(k.max() < l.min())
+        ok &= faster
+        out.append(f"B = {r['B']:6d}  T = {r['T']:4d}  ({r['bytes'] / 1e6:8.1f} MB algorithmic, {r['sets']} buffer sets of {r['set_mb']:.0f} MB)")
+        out.append(f"    kernel      {km:10.1f} us  [{k.min():.1f} .. {k.max():.1f}]   {r['bytes'] / km / 1e6:.2f} TB/s = {share:.3f} of the 8 TB/s peak (memory-bound)")
+        out.append(f"    torch loop  {lm:10.1f} us  [{l.min():.1f} .. {l.max():.1f}]   ratio {lm / km:.1f}x   kernel faster in every repeat: {'yes' if faster else 'NO'}"
+                   f"   (max |kernel - loop| = {r['max_abs_diff']:.2e})")
+    return "\n".join(out) + "\n", ok
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gae_time.txt"))
+    ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--repeats", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("tools/gae_time.py needs a GPU: a time measured anywhere else says nothing")
+    lib = _abi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = []
+    for B, T in SHAPES:
+        rows.append(measure(lib, B, T, args.seconds, args.repeats, dev))
+        torch.cuda.empty_cache()
+        print(report(rows[-1:])[0], flush=True)
+    text, ok = report(rows)
+    with open(args.out, "w") as f:
+        f.write(text)
+    sys.exit(0 if ok else 1)
