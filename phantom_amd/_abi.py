@@ -136,7 +136,15 @@ class PhxGaeIO(C.Structure):
         (n, C.c_void_p) for n in ("reward", "vf_pred", "vf_next", "terminated", "truncated", "advantage", "value_target")]
 
 
+class PhxGaeMaskedIO(C.Structure):
+    """phx_gae_masked_io (include/phantom_amd_gae.h): the planes of one phx_gae_masked call"""
+    _fields_ = [("T", C.c_int32), ("reserved0", C.c_int32), ("N", C.c_int64), ("gamma", C.c_float), ("lambda_", C.c_float)] + [
+        (n, C.c_void_p) for n in ("reward", "vf_pred", "vf_next", "terminated", "truncated", "acted", "reward_valid", "advantage",
+                                  "value_target", "reward_sum")]
+
+
 GAE_KERNEL = "phx_gae_kernel"
+GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -232,10 +240,12 @@ def bind_signatures(lib):
 
 
 def bind_gae(lib):
-    """restype / argtypes of include/phantom_amd_gae.h's entry point: libphantom_amd.so only (the CPU restatement behind
-    phantom_amd.h's symbols has no such function, so this is not part of bind_signatures)"""
+    """restype / argtypes of include/phantom_amd_gae.h's entry points: libphantom_amd.so only (the CPU restatement behind
+    phantom_amd.h's symbols has no such functions, so this is not part of bind_signatures)"""
     lib.phx_gae.restype = C.c_int32
     lib.phx_gae.argtypes = [C.POINTER(PhxGaeIO), C.c_void_p]
+    lib.phx_gae_masked.restype = C.c_int32
+    lib.phx_gae_masked.argtypes = [C.POINTER(PhxGaeMaskedIO), C.c_void_p]
     return lib
 
 

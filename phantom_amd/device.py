@@ -691,6 +691,45 @@ class DeviceEnv:
             self._check(self.lib.phx_gae(C.byref(io), self._stream()), "phx_gae")
         return adv, vt
 
+    def gae_masked(self, rewards, truncations, vf_pred=None, vf_next=None, terminations=None, acted=None, reward_valid=None,
+                   gamma: float = 0.99, lambda_: float = 1.0, out=None):
+        """``(advantages, value_targets, trajectory_rewards)`` of a time-major fragment whose per-agent trajectories have holes
+        (FSM / Stackelberg envs), in ONE launch on the current stream (phx_gae_masked, include/phantom_amd_gae.h).  The planes are
+        ``gae()``'s, plus ``acted`` u8 (!= 0: the agent held an observation and acted at step t -- a trajectory row) and
+        ``reward_valid`` u8 as a rollout wrote it (only the value 1 counts); each missing one reads as all one.  At a trajectory row
+        ``trajectory_rewards`` is the sum of the rewards that arrived from that row until the agent's next trajectory row or the first
+        cut row (a done flag, the fragment's last row), whichever comes first; that cut row's ``terminations`` flag and ``vf_next``
+        element give the bootstrap value, and the advantage chain links trajectory rows only.  Rows that are no trajectory rows
+        hold +0.0 in all three results.  ``vf_pred`` is read at trajectory rows only, ``rewards`` where ``reward_valid == 1``,
+        ``vf_next`` at the closing cut rows.  ``out``: the three f32 result tensors, 16-byte aligned (allocated here when None)."""
+        torch = _torch()
+        f32, u8 = torch.float32, torch.uint8
+        if rewards is None or rewards.dim() < 2:
+            raise ValueError("gae_masked: `rewards` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(rewards.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"gae_masked: `rewards` has shape {shape}: T and N must be >= 1")
+        if not (0.0 <= gamma <= 1.0 and 0.0 <= lambda_ <= 1.0):
+            raise ValueError(f"gae_masked: gamma = {gamma} and lambda_ = {lambda_} must lie in [0, 1]")
+        check_tensor("gae_masked", "rewards", rewards, f32, shape, device=self.device)
+        check_tensor("gae_masked", "truncations", truncations, u8, shape, device=self.device)
+        for name, x, dtype in (("vf_pred", vf_pred, f32), ("vf_next", vf_next, f32), ("terminations", terminations, u8),
+                               ("acted", acted, u8), ("reward_valid", reward_valid, u8)):
+            if x is not None:
+                check_tensor("gae_masked", name, x, dtype, shape, device=self.device)
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=f32, device=self.device) for _ in range(3))
+        adv, vt, rs = out
+        for i, x in enumerate(out):
+            check_tensor("gae_masked", f"out[{i}]", x, f32, shape, align=16, device=self.device)
+        io = _abi.PhxGaeMaskedIO(T=T, N=N, gamma=gamma, lambda_=lambda_, reward=_ptr(rewards), vf_pred=_ptr(vf_pred), vf_next=_ptr(vf_next),
+                                 terminated=_ptr(terminations), truncated=_ptr(truncations), acted=_ptr(acted),
+                                 reward_valid=_ptr(reward_valid), advantage=_ptr(adv), value_target=_ptr(vt), reward_sum=_ptr(rs))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_gae_masked(C.byref(io), self._stream()), "phx_gae_masked")
+        return adv, vt, rs
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

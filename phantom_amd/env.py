@@ -299,11 +299,11 @@ class PhantomEnv:
     def _host_reset(self, mask=None):
         sel = slice(None) if mask is None else np.asarray(mask, dtype=bool)
         self._h_step[sel] = 0
-        self._obs_state = ("dev", None)                          # the strategic agents' current observation = the device's obs buffer
+        self._obs_state = ("dev", None, None)                    # the strategic agents' current observation (and its validity) = the device's obs buffers
 
     def _host_advance(self):
         self._h_step += 1
-        self._obs_state = ("dev", None)
+        self._obs_state = ("dev", None, None)
 
     def _launch_step(self, dev, actions, action_valid, exo):
         """one device step; FiniteStateMachineEnv splits it around host-side stage handlers (phx_step_begin / phx_step_end)"""
@@ -415,7 +415,8 @@ class PhantomEnv:
             exo_ok = True                                       # (randint(5) draws: the store-wave kernel may replay them, PHX_RH_EXO_IN_DOMAIN)
         traj = self._device().rollout(T, actions, exo, out, exo_in_domain=exo_ok, policy=policy, noise=noise)
         self._sync_host_state()
-        self._obs_state = ("traj", traj.last_obs)               # what the strategic agents observe now (sample() starts from it)
+        # what the strategic agents observe now, and who of them does (sample() starts from it)
+        self._obs_state = ("traj", traj.last_obs, None if traj.obs_valid is None else traj.obs_valid[T - 1])
         return traj
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
@@ -427,9 +428,18 @@ class PhantomEnv:
 
         The fragment is produced one episode piece per launch (a piece ends where the episode ends: the kernel's auto-reset
         then leaves the NEXT episode's reset observation in ``last_obs``), transposed on the device and copied through pinned
-        host buffers.  Plain envs (every strategic agent observes every step); ``reset()`` first.
+        host buffers.  ``reset()`` first.
 
-        ``policy``: an ``MLPPolicy`` evaluated on the device (on-policy sampling, plain supply chains); ``explore=True`` samples its
+        FSM and Stackelberg envs whose strategic agents always return an observation when asked (shops, sellers, buyers; envs with
+        advertisers raise NotImplementedError): their step dicts omit keys, so an agent's trajectory has holes.  The batch then carries
+        ``new_obs_valid`` (the rollout's ``obs_valid`` plane), ``reward_valid`` and ``obs_valid`` = who acted: the validity the previous
+        ``reset()`` / ``step`` / ``sample()`` left at the first row, ``reset()``'s at an episode's first row, ``new_obs_valid[t - 1]``
+        elsewhere.  One ``DeviceEnv.gae_masked`` launch gives ``trajectory_rewards`` -- at the rows where an agent acted, the sum of the
+        rewards that arrived until its next observation (the reference hands a reward over with the NEXT observation; ``rewards`` stays
+        step-aligned) -- which ``to_sample_batches()`` takes as its ``rewards`` column.  ``stage`` / ``stage_ids`` come from the host's
+        own transition table; an env with rule-form stage handlers, whose transitions depend on agent state, gets ``stage = None``.
+
+        ``policy``: an ``MLPPolicy`` evaluated on the device (on-policy sampling, plain supply chains only: ValueError otherwise); ``explore=True`` samples its
         Gaussian (a stochastic policy) with noise from ``torch.randn(generator=generator)`` -- without a generator the env's own, seeded
         from (seed, env_offset), so that shards draw independently -- and the batch carries ``raw_actions`` / ``action_logp`` /
         ``dist_inputs`` (RLlib's actions, action_logp, action_prob and action_dist_inputs columns).
@@ -438,7 +448,11 @@ class PhantomEnv:
         called once on every row's ``obs`` and once on ``new_obs`` of the rows where a trajectory can be cut (each piece's last row:
         an episode's end or the fragment's); one ``DeviceEnv.gae`` launch then turns rewards, done flags and the two value planes
         into generalised advantage estimates with ``gamma`` / ``lambda_`` (RLlib's ``compute_advantages``), and the batch carries
-        ``vf_preds`` / ``advantages`` / ``value_targets``.  Without ``value_fn`` nothing of this runs."""
+        ``vf_preds`` / ``advantages`` / ``value_targets``.  Without ``value_fn`` nothing of this runs on a plain env.  On an FSM /
+        Stackelberg env the critic sees +0.0 in place of ``obs`` rows where the agent holds no observation, ``vf_next`` at a piece's last
+        row is the critic on the observation the agent holds there (``new_obs`` of the piece's latest row with ``new_obs_valid``, else
+        the piece's first observation), and the launch is ``gae_masked``; without ``value_fn`` the same launch runs without value planes
+        (``lambda_ = 1``) for ``trajectory_rewards`` alone."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -446,9 +460,14 @@ class PhantomEnv:
         if explore and (policy is None or not policy.stochastic):
             raise ValueError("sample: explore=True needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
         dev = self._device()
-        if self.spec.env_type != _abi.ENV_PLAIN or dev._needs_valid_planes():
-            raise NotImplementedError("PhantomEnv.sample: plain envs only (FSM / Stackelberg dicts omit keys: use rollout() and "
-                                      "phantom_amd.rollout.fragment_from_arrays with the validity planes)")
+        masked = self.spec.env_type != _abi.ENV_PLAIN            # per-agent trajectories with holes: validity planes, phx_gae_masked
+        kinds = self.spec.kind[self.spec.strategic_idx]
+        if (self.spec.kind == _abi.KIND_ADVERTISER).any() or (masked and not np.isin(kinds, (_abi.KIND_SHOP, _abi.KIND_SELLER, _abi.KIND_BUYER)).all()):
+            raise NotImplementedError("PhantomEnv.sample: envs whose strategic agents always return an observation when asked (shops, "
+                                      "sellers, buyers); for others use rollout() and phantom_amd.rollout.fragment_from_arrays with "
+                                      "the validity planes")
+        if masked and policy is not None:
+            raise ValueError("sample: `policy` (a device-evaluated MLPPolicy) serves plain envs only; replay `actions` on FSM / Stackelberg envs")
         if not (self._h_step == self._h_step[0]).all():
             raise ValueError("sample() needs every env instance at the same step (after masked resets use rollout())")
         cur = int(self._h_step[0])
@@ -468,12 +487,20 @@ class PhantomEnv:
             noise = torch.randn((T, B, S), generator=gen, dtype=torch.float32, device=dev.device)
             raw, logp = torch.empty_like(act), torch.empty_like(act)
             dist = torch.empty((T, B, S, 2), dtype=torch.float32, device=dev.device)
+        acted = nvalid = rvalid = cur_valid = reset_valid = None
+        stages = []
+        if masked:
+            acted, nvalid, rvalid = torch.empty_like(term), torch.empty_like(term), torch.empty_like(term)
+            cur_valid = self._cur_obs_valid_tensor()
+            reset_valid = torch.from_numpy(self._reset_obs_valid()).to(dev.device).expand(B, S)
         done, ep, piece_ends = 0, ep0, []
         while done < T:
             n = min(T - done, N - cur)
             # (a slice of the caller's tensor may start off a 16-byte boundary -- B * S * 4 or B * n_exo not a multiple of 16: fine since
             #  ABI 9, the replayed inputs are read element by element)
             piece = lambda x: None if x is None else x[done:done + n]
+            if masked:
+                stages.append(self._stage_walk(n))               # (before the launch: the rollout moves the host's stage mirror)
             tr = self.rollout(n, piece(actions), piece(exo), policy=policy, noise=piece(noise))
             sl = slice(done, done + n)
             new_obs[sl], act[sl], rew[sl], term[sl], trunc[sl] = tr.observations, tr.actions, tr.rewards, tr.terminations, tr.truncations
@@ -481,6 +508,11 @@ class PhantomEnv:
                 raw[sl], logp[sl], dist[sl] = tr.raw_actions, tr.action_logp, tr.dist_inputs
             obs[done] = cur_obs
             obs[done + 1:done + n] = tr.observations[:n - 1]
+            if masked:                                           # who acted: who held an observation when the step began
+                nvalid[sl], rvalid[sl] = tr.obs_valid, tr.reward_valid
+                acted[done] = cur_valid
+                acted[done + 1:done + n] = tr.obs_valid[:n - 1]
+                cur_valid = reset_valid if cur + n == N else tr.obs_valid[n - 1]
             t_in_ep[sl] = np.arange(cur, cur + n); eps[sl] = ep
             cur_obs = tr.last_obs
             cur += n
@@ -494,12 +526,15 @@ class PhantomEnv:
                 "truncateds": am(trunc)}
         if explore:
             cols.update(raw_actions=am(raw), action_logp=am(logp), dist_inputs=am(dist))
-        if value_fn is not None:
-            def values(x):                                                    # f32 [R, B, S, D] -> the critic's f32 [R, B, S]
-                v = value_fn(x.reshape(-1, D))
-                if v.dtype != torch.float32 or v.numel() != x.shape[0] * B * S:
-                    raise ValueError(f"sample: `value_fn` must map f32 [M, {D}] to f32 [M] or [M, 1], got {v.dtype} {tuple(v.shape)}")
-                return v.detach().reshape(x.shape[0], B, S).contiguous()
+        if masked:
+            cols.update(obs_valid=am(acted), new_obs_valid=am(nvalid), reward_valid=am(rvalid))
+
+        def values(x):                                                        # f32 [R, B, S, D] -> the critic's f32 [R, B, S]
+            v = value_fn(x.reshape(-1, D))
+            if v.dtype != torch.float32 or v.numel() != x.shape[0] * B * S:
+                raise ValueError(f"sample: `value_fn` must map f32 [M, {D}] to f32 [M] or [M, 1], got {v.dtype} {tuple(v.shape)}")
+            return v.detach().reshape(x.shape[0], B, S).contiguous()
+        if value_fn is not None and not masked:
             with torch.no_grad():
                 vf = values(obs)
                 ends = torch.as_tensor(piece_ends, device=dev.device)
@@ -507,14 +542,37 @@ class PhantomEnv:
                 vf_next[ends] = values(new_obs[ends])
             adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
             cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
+        elif masked:
+            vf = vf_next = None
+            if value_fn is not None:
+                with torch.no_grad():
+                    # rows where the agent holds no observation: +0.0 to the critic (their values are never read)
+                    vf = values(torch.where((acted != 0)[..., None], obs, torch.zeros((), dtype=obs.dtype, device=dev.device)))
+                    vf_next = torch.zeros_like(vf)
+                    first = 0
+                    for last in piece_ends:                                   # the observation each agent holds at the piece's last row
+                        rows = torch.arange(first, last + 1, device=dev.device)[:, None, None]
+                        latest = torch.where(nvalid[first:last + 1] != 0, rows, rows.new_full((), -1)).amax(dim=0)      # [B, S]
+                        idx = (latest.clamp(min=first) - first)[None, :, :, None].expand(1, B, S, D)
+                        held = torch.where((latest >= 0)[..., None], new_obs[first:last + 1].gather(0, idx)[0], obs[first])
+                        vf_next[last] = values(held[None])[0]
+                        first = last + 1
+            adv, vt, rs = dev.gae_masked(rew, trunc, vf, vf_next, term, acted, rvalid, gamma, lambda_ if value_fn is not None else 1.0)
+            cols.update(trajectory_rewards=am(rs))
+            if value_fn is not None:
+                cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
+        stage = np.concatenate(stages, axis=1) if stages and all(x is not None for x in stages) else None
         return FragmentBatch(ids, host["obs"], host["new_obs"], host["actions"], host["rewards"], host["terminateds"].astype(bool),
                              host["truncateds"].astype(bool), np.broadcast_to(t_in_ep, (B, T)).copy(),
                              (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64),
+                             obs_valid=host.get("obs_valid"), new_obs_valid=host.get("new_obs_valid"), reward_valid=host.get("reward_valid"),
+                             stage=stage, stage_ids=self._stage_ids() if stage is not None else None,
                              never_finishes_alone=dev.never_terminates(), raw_actions=host.get("raw_actions"),
                              action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"), vf_preds=host.get("vf_preds"),
-                             advantages=host.get("advantages"), value_targets=host.get("value_targets"))
+                             advantages=host.get("advantages"), value_targets=host.get("value_targets"),
+                             trajectory_rewards=host.get("trajectory_rewards"))
 
     def _noise_generator(self, device):
         """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""
@@ -529,8 +587,42 @@ class PhantomEnv:
 
     def _cur_obs_tensor(self):
         """the observation the strategic agents hold right now (what reset / the last step / the last rollout returned), on the device"""
-        kind, t = getattr(self, "_obs_state", ("dev", None))
+        kind, t, _ = getattr(self, "_obs_state", ("dev", None, None))
         return self._device().obs if kind == "dev" else t
+
+    def _reset_obs_valid(self):
+        """u8 [S]: who gets an observation from ``reset()`` -- the strategic agents acting in the initial stage (fsm.py:237-251), the
+        leaders (stackelberg.py:95-109), everybody on a plain env; for kinds that always return an observation when asked"""
+        spec = self.spec
+        rank = {int(a): s for s, a in enumerate(spec.strategic_idx)}
+        if spec.env_type == _abi.ENV_FSM:
+            st = spec.initial_stage
+            first = spec.stage_act_idx[spec.stage_act_ptr[st]:spec.stage_act_ptr[st + 1]]
+        elif spec.env_type == _abi.ENV_STACKELBERG:
+            first = spec.leaders
+        else:
+            first = spec.strategic_idx
+        valid = np.zeros(spec.n_strategic, dtype=np.uint8)
+        valid[[rank[int(a)] for a in first if int(a) in rank]] = 1
+        return valid
+
+    def _cur_obs_valid_tensor(self):
+        """u8 [B, S] on the device: which strategic agents hold an observation right now (the validity reset / the last step / the last
+        rollout left; an env instance whose last rollout ended with its episode holds the next episode's reset observation)"""
+        import torch
+        dev = self._device()
+        kind, _, valid = getattr(self, "_obs_state", ("dev", None, None))
+        if kind == "dev":
+            return dev.obs_valid
+        fresh = torch.from_numpy(self._h_step == 0).to(dev.device)
+        return torch.where(fresh[:, None], torch.from_numpy(self._reset_obs_valid()).to(dev.device)[None, :], valid)
+
+    def _stage_walk(self, n: int):
+        """FiniteStateMachineEnv: the stages of the next n steps"""
+        return None
+
+    def _stage_ids(self):
+        return None
 
     def _to_pinned(self, tensors):
         """device tensors -> numpy arrays through pinned host buffers (kept per name and shape), one synchronisation"""

@@ -328,6 +328,7 @@ class FiniteStateMachineEnv(PhantomEnv):
         sel = slice(None) if mask is None else np.asarray(mask, dtype=bool)
         self._h_step[sel] = 0
         self._h_stage[sel] = self._stage_index[self._initial_stage]      # fsm.py:217
+        self._obs_state = ("dev", None, None)
 
     def _sync_host_state(self):
         super()._sync_host_state()
@@ -394,8 +395,27 @@ class FiniteStateMachineEnv(PhantomEnv):
                                       "declared state-independent (@phantom_amd.state_independent) and tabulated")
         return super().rollout(*args, **kwargs)
 
+    def _stage_walk(self, n: int):
+        """i32 [B, n]: the stages the next n steps of the current episode run in, from the host's own transition table (what
+        _host_advance does step by step), without advancing anything; None where the device decides (rule-form handlers)"""
+        if self._rule_handlers or self._has_handlers:
+            return None
+        self._refresh_stage()
+        nxt = np.asarray([self._stage_index[s.next_stages[0]] if s.next_stages else 0 for s in self._stage_list])
+        st, step = self._h_stage.copy(), self._h_step.copy()
+        out = np.empty((self.batch_size, n), dtype=np.int32)
+        for i in range(n):
+            out[:, i] = st
+            step += 1
+            st = self._stage_tab[st, np.minimum(step, self.num_steps)].astype(np.int64) if self._stage_tab is not None else nxt[st]
+        return out
+
+    def _stage_ids(self):
+        return [s.id for s in self._stage_list]
+
     def _host_advance(self):
         self._h_step += 1
+        self._obs_state = ("dev", None, None)
         nxt = np.asarray([self._stage_index[s.next_stages[0]] if s.next_stages else 0 for s in self._stage_list])
         if self._rule_handlers:                                          # the device chose: read back when somebody asks
             self._stage_dirty = True

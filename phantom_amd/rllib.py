@@ -414,7 +414,8 @@ class BatchedBaseEnv(_BaseEnvBase):
         column dicts (phantom_amd.rollout.FragmentBatch.to_sample_batches) -- no python object per (env, agent, step).
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
         ``generator``: on-policy sampling with a device policy, deterministic or exploring; ``value_fn`` / ``gamma`` / ``lambda_``: a critic, for the
-        ``vf_preds`` / ``advantages`` / ``value_targets`` columns (PhantomEnv.sample)."""
+        ``vf_preds`` / ``advantages`` / ``value_targets`` columns (PhantomEnv.sample).  On FSM and Stackelberg envs (shops, sellers, buyers)
+        the columns hold the rows where the agent acted, and ``rewards`` is what arrived until its next observation (``trajectory_rewards``)."""
         return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
                                lambda_=lambda_).to_sample_batches(policy_mapping_fn)
 

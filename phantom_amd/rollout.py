@@ -166,7 +166,9 @@ class FragmentBatch:
     ``raw_actions`` f32 [B, S, T] the Gaussian draw z (``actions`` stays what the env took: clip(out_scale z + out_bias))
     ``action_logp`` f32 [B, S, T] log N(z; mean, exp(log_std))              ``dist_inputs`` f32 [B, S, T, 2] (mean, log_std)
     a fragment sampled with a critic (PhantomEnv.sample(value_fn=...)), else None -- RLlib's columns of the same names:
-    ``vf_preds`` f32 [B, S, T] V(obs)       ``advantages`` / ``value_targets`` f32 [B, S, T] (DeviceEnv.gae)
+    ``vf_preds`` f32 [B, S, T] V(obs)       ``advantages`` / ``value_targets`` f32 [B, S, T] (DeviceEnv.gae / gae_masked)
+    ``trajectory_rewards`` f32 [B, S, T] or None (FSM / Stackelberg fragments of PhantomEnv.sample): at the rows where the agent
+    acted, the sum of the rewards that arrived until its next observation (DeviceEnv.gae_masked); ``rewards`` stays step-aligned
     """
 
     COLUMNS = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
@@ -174,7 +176,7 @@ class FragmentBatch:
     def __init__(self, agent_ids, obs, new_obs, actions, rewards, terminateds, truncateds, t, eps_id,
                  obs_valid=None, new_obs_valid=None, reward_valid=None, stage=None, stage_ids=None,
                  action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
-                 dist_inputs=None, vf_preds=None, advantages=None, value_targets=None):
+                 dist_inputs=None, vf_preds=None, advantages=None, value_targets=None, trajectory_rewards=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -185,6 +187,7 @@ class FragmentBatch:
         self.never_finishes_alone = never_finishes_alone
         self.raw_actions, self.action_logp, self.dist_inputs = raw_actions, action_logp, dist_inputs
         self.vf_preds, self.advantages, self.value_targets = vf_preds, advantages, value_targets
+        self.trajectory_rewards = trajectory_rewards
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
     # ---- RLlib-shaped exit -------------------------------------------------------------------------------------------
@@ -195,7 +198,8 @@ class FragmentBatch:
         out as reshaped VIEWS of the host arrays (no copy); envs whose dicts omit keys (FSM / Stackelberg) drop the rows of
         absent observations (boolean mask: a copy).  An exploring fragment's ``actions`` column is the raw draw z (what RLlib's
         sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``; a fragment with
-        ``vf_preds`` / ``advantages`` / ``value_targets`` has the columns of those names."""
+        ``vf_preds`` / ``advantages`` / ``value_targets`` has the columns of those names; a fragment with ``trajectory_rewards``
+        takes its ``rewards`` column from them (an action's reward is what arrived until the agent's next observation)."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
         for s, aid in enumerate(self.agent_ids):
@@ -223,6 +227,8 @@ class FragmentBatch:
                 cols["action_logp"] = sel(self.action_logp).reshape(-1)
                 cols["action_prob"] = np.exp(cols["action_logp"])
                 cols["action_dist_inputs"] = sel(self.dist_inputs).reshape(B * n * T, -1)
+            if self.trajectory_rewards is not None:
+                cols["rewards"] = sel(self.trajectory_rewards).reshape(-1)
             for name in ("vf_preds", "advantages", "value_targets"):
                 if getattr(self, name) is not None:
                     cols[name] = sel(getattr(self, name)).reshape(-1)

@@ -1,10 +1,15 @@
 """phx_gae (include/phantom_amd_gae.h) against the torch reverse loop a user would write without it, at SC64's trajectory planes.
     python tools/gae_time.py [--out profiles/gae_time.txt] [--seconds 0.5] [--repeats 5]
+    python tools/gae_time.py --masked [--out profiles/gae_masked_time.txt]      phx_gae_masked against phx_gae, see below
 GPU only: no device, no number.  Per shape the two are timed in ONE process, alternating, `repeats` times each over a window of
 `seconds`, with HIP events; the kernel rotates over buffer sets whose total exceeds 256 MB, so that its planes come from HBM and not
 from the Infinity Cache.  Roofline: the bytes the ALGORITHM needs, from the shapes -- 4 B per element of a value or output plane, 1 B
 per element of a flag plane, a plane counted only when it is given, vf_next counted as the rows the definition reads -- over the
-8 TB/s peak, as bench.py's `roofline` does."""
+8 TB/s peak, as bench.py's `roofline` does.
+--masked: phx_gae_masked_kernel at the same shapes, in the same process, alternating with phx_gae_kernel (the yardstick) under the same
+rotation and windows, every plane given, with two acted planes: all one (reward_valid all one: the result is phx_gae's, checked bit for
+bit) and alternating rows (an FSM supply chain: the shops act in even rows, their rewards arrive in odd rows and at an episode's end).
+It moves 28 B per element against phx_gae's 22 (two more flag bytes, one more f32 output): 1.27 is the expected ratio."""
 import argparse
 import ctypes as C
 import os
@@ -105,6 +110,74 @@ def measure(lib, B, T, seconds, repeats, dev):
     return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, bytes=by, kernel_us=ks, loop_us=ls, max_abs_diff=err)
 
 
+def measure_masked(lib, B, T, seconds, repeats, dev):
+    N = B * S
+    gen = torch.Generator(device=dev).manual_seed(0)
+    one = T * N * 28
+    n_sets = max(2, -(-(256 << 20) // one) + 1)           # working set beyond the 256 MiB Infinity Cache
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sets, plain, masked = [], [], {"all one": [], "alternating rows": []}
+    for _ in range(n_sets):
+        b = buffer_set(T, N, dev, gen)
+        ones = torch.ones((T, N), dtype=torch.uint8, device=dev)
+        alt, rv_alt = torch.zeros_like(ones), torch.zeros_like(ones)
+        alt[0::2] = 1
+        rv_alt[1::2] = 1; rv_alt[EPISODE - 1::EPISODE] = 1
+        extra = dict(acted_one=ones, rv_one=ones.clone(), acted_alt=alt, rv_alt=rv_alt, reward_sum=torch.empty((T, N), device=dev),
+                     adv_ref=torch.empty((T, N), device=dev), vt_ref=torch.empty((T, N), device=dev))
+        sets.append((b, extra))
+        plain.append(_abi.PhxGaeIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, **{**{k: v.data_ptr() for k, v in b.items()},
+                                                                              "advantage": extra["adv_ref"].data_ptr(),
+                                                                              "value_target": extra["vt_ref"].data_ptr()}))
+        for name, a, rv in (("all one", "acted_one", "rv_one"), ("alternating rows", "acted_alt", "rv_alt")):
+            masked[name].append(_abi.PhxGaeMaskedIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, acted=extra[a].data_ptr(), reward_valid=extra[rv].data_ptr(),
+                                                    reward_sum=extra["reward_sum"].data_ptr(), **{k: v.data_ptr() for k, v in b.items()}))
+
+    def caller(fn, ios):
+        refs = [C.byref(io) for io in ios]
+
+        def call(i):
+            if fn(refs[i % n_sets], stream) != 0:
+                raise RuntimeError(lib.phx_last_error().decode())
+        return call
+
+    calls = {"phx_gae_kernel": caller(lib.phx_gae, plain)}
+    calls.update({f"phx_gae_masked_kernel, acted {k}": caller(lib.phx_gae_masked, v) for k, v in masked.items()})
+    b, extra = sets[0]
+    calls["phx_gae_kernel"](0); calls["phx_gae_masked_kernel, acted all one"](0); torch.cuda.synchronize()
+    same = all(bool((x.view(torch.int32) == y.view(torch.int32)).all()) for x, y in
+               ((b["advantage"], extra["adv_ref"]), (b["value_target"], extra["vt_ref"]), (extra["reward_sum"], b["reward"])))
+    if not same:
+        raise RuntimeError("phx_gae_masked with all-one planes and phx_gae disagree")
+    for fn in calls.values():
+        for i in range(n_sets):
+            fn(i)
+    us = {k: [] for k in calls}
+    for _ in range(repeats):                              # alternating
+        for k, fn in calls.items():
+            us[k].append(window(fn, seconds)[0])
+    return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, us=us)
+
+
+def report_masked(rows):
+    out = ["phx_gae_masked_kernel against phx_gae_kernel (tools/gae_time.py --masked); SC64 planes, N = 9 B columns, episodes of 100 steps,",
+           f"gamma = {GAMMA}, lambda = {LAMBDA}, every plane given: 28 B per element moved against 22 (expected ratio 1.27).  One process, alternating,",
+           "the same buffer rotation and windows.  Times: median [min .. max] over the repeats, microseconds per call; spread = (max - min) / median.",
+           "With all-one planes the three outputs equal phx_gae's and the reward plane bit for bit (checked before timing).",
+           f"device: {torch.cuda.get_device_name()}", ""]
+    for r in rows:
+        el = r["T"] * r["N"]
+        base = float(np.median(r["us"]["phx_gae_kernel"]))
+        out.append(f"B = {r['B']:6d}  T = {r['T']:4d}  ({el / 1e6:.1f} M elements, {r['sets']} buffer sets of {r['set_mb']:.0f} MB)")
+        for k, v in r["us"].items():
+            v = np.array(v)
+            m = float(np.median(v))
+            per = 22 if k == "phx_gae_kernel" else 28
+            out.append(f"    {k:44s} {m:9.1f} us  [{v.min():.1f} .. {v.max():.1f}]  spread {(v.max() - v.min()) / m:.3f}   {el * per / m / 1e6:.2f} TB/s moved"
+                       f" = {el * per / (m * 1e-6) / PEAK_BYTES_PER_S:.3f} of the peak   ratio to phx_gae_kernel {m / base:.3f}")
+    return "\n".join(out) + "\n"
+
+
 def report(rows):
     out = ["phx_gae_kernel against the torch reverse loop (tools/gae_time.py); SC64 planes, N = 9 B columns, episodes of 100 steps,",
            f"gamma = {GAMMA}, lambda = {LAMBDA}, every plane given.  Times: median [min .. max] over the repeats, microseconds per call.",
@@ -125,7 +198,8 @@ def report(rows):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gae_time.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--masked", action="store_true", help="phx_gae_masked_kernel against phx_gae_kernel")
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
@@ -134,11 +208,19 @@ if __name__ == "__main__":
     lib = _abi.load_library()
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = []
+    if args.masked:
+        for B, T in SHAPES:
+            rows.append(measure_masked(lib, B, T, args.seconds, args.repeats, dev))
+            torch.cuda.empty_cache()
+            print(report_masked(rows[-1:]), flush=True)
+        with open(args.out or os.path.join(ROOT, "profiles", "gae_masked_time.txt"), "w") as f:
+            f.write(report_masked(rows))
+        sys.exit(0)
     for B, T in SHAPES:
         rows.append(measure(lib, B, T, args.seconds, args.repeats, dev))
         torch.cuda.empty_cache()
         print(report(rows[-1:])[0], flush=True)
     text, ok = report(rows)
-    with open(args.out, "w") as f:
+    with open(args.out or os.path.join(ROOT, "profiles", "gae_time.txt"), "w") as f:
         f.write(text)
     sys.exit(0 if ok else 1)
