@@ -87,3 +87,16 @@ critic = torch.nn.Sequential(torch.nn.Linear(3, 64), torch.nn.Tanh(), torch.nn.L
 batch = env.sample(100, policy=pol, explore=True, value_fn=critic, gamma=0.99, lambda_=0.95)
 cols = batch.to_sample_batches()["default_policy"]
 print("PPO batch:", cols["advantages"].shape[0], "rows from", env._device().last_kernel(), "| columns", sorted(cols))
+
+# 9. an APPO / IMPALA learner's batch: the sampler's policy is a few updates behind the learner's, so the learner hands over its CURRENT
+#    log-density of the recorded draws and ONE launch (phx_vtrace) corrects for the gap -- RLlib's vtrace from_importance_weights on the device
+learner = torch.nn.Sequential(torch.nn.Linear(3, 32), torch.nn.Tanh(), torch.nn.Linear(32, 2)).to(env._device().device)
+
+def target_logp(obs, raw_actions):                       # log N(raw_action; mean(obs), exp(log_std(obs))) under the learner's weights
+    mean, log_std = learner(obs).unbind(-1)
+    return -0.5 * ((raw_actions - mean) * torch.exp(-log_std)) ** 2 - log_std - 0.5 * float(np.log(2 * np.pi))
+
+batch = env.sample(100, policy=pol, explore=True, value_fn=critic, gamma=0.99, target_logp_fn=target_logp, vtrace_clip=(1.0, 1.0, 1.0))
+cols = batch.to_sample_batches()["default_policy"]
+print("APPO batch:", cols["vtrace_vs"].shape[0], "rows from", env._device().last_kernel(), "| V-trace columns",
+      sorted(k for k in cols if k.startswith("vtrace") or k in ("vf_preds", "target_logp", "action_logp")))

@@ -2,7 +2,7 @@
 
 Host side: Python classes with the reference's names and signatures (PhantomEnv, Network,
 Agent, ...).  Device side: hand-written HIP kernels for gfx950 behind a C ABI
-(include/phantom_amd.h, include/phantom_amd_gae.h, phantom_amd/csrc).  See DESIGN.md and INTEGRATION.md.
+(include/phantom_amd.h, include/phantom_amd_gae.h, include/phantom_amd_vtrace.h, phantom_amd/csrc).  See DESIGN.md and INTEGRATION.md.
 """
 __version__ = "0.1.0"
 
@@ -31,5 +31,5 @@ from .views import AgentView, Context, EnvView, FSMEnvView, View
 from . import ads_market, metrics, policy, rllib
 from .policy import MLPPolicy
 from .distributed import all_gather_trajectory, make_sharded_env, shard_batch
-from .device import DeviceEnv            # DeviceEnv.gae: advantages and value targets of a fragment (include/phantom_amd_gae.h)
+from .device import DeviceEnv            # DeviceEnv.gae / gae_masked / vtrace: a learner's targets of a fragment (include/phantom_amd_gae.h, _vtrace.h)
 from .rollout import FragmentBatch       # what PhantomEnv.sample returns (vf_preds / advantages / value_targets with value_fn=...)

@@ -143,13 +143,23 @@ class PhxGaeMaskedIO(C.Structure):
                                   "value_target", "reward_sum")]
 
 
+class PhxVtraceIO(C.Structure):
+    """phx_vtrace_io (include/phantom_amd_vtrace.h): the planes of one phx_vtrace call"""
+    _fields_ = [("T", C.c_int32), ("reserved0", C.c_int32), ("N", C.c_int64), ("gamma", C.c_float), ("lambda_", C.c_float),
+                ("rho_bar", C.c_float), ("c_bar", C.c_float), ("pg_rho_bar", C.c_float), ("reserved1", C.c_float)] + [
+        (n, C.c_void_p) for n in ("reward", "vf_pred", "vf_next", "behaviour_logp", "target_logp", "terminated", "truncated", "vs",
+                                  "pg_advantage")]
+
+
 GAE_KERNEL = "phx_gae_kernel"
 GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
+VTRACE_KERNEL = "phx_vtrace_kernel"
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
 
 assert C.sizeof(PhxMsgRec) == 16
+assert C.sizeof(PhxVtraceIO) == 112      # (stated in include/phantom_amd_vtrace.h)
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -249,6 +259,13 @@ def bind_gae(lib):
     return lib
 
 
+def bind_vtrace(lib):
+    """restype / argtypes of include/phantom_amd_vtrace.h's entry point: libphantom_amd.so only, like bind_gae"""
+    lib.phx_vtrace.restype = C.c_int32
+    lib.phx_vtrace.argtypes = [C.POINTER(PhxVtraceIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -265,6 +282,7 @@ def load_library():
     lib = C.CDLL(LIB_PATH)
     bind_signatures(lib)
     bind_gae(lib)
+    bind_vtrace(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

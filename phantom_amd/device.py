@@ -730,6 +730,52 @@ class DeviceEnv:
             self._check(self.lib.phx_gae_masked(C.byref(io), self._stream()), "phx_gae_masked")
         return adv, vt, rs
 
+    def vtrace(self, rewards, truncations, vf_pred, behaviour_logp, target_logp, vf_next=None, terminations=None,
+               gamma: float = 0.99, lambda_: float = 1.0, clip_rho_threshold: float = 1.0, clip_c_threshold: float = 1.0,
+               clip_pg_rho_threshold: float = 1.0, out=None):
+        """``(vs, pg_advantages)`` of a time-major fragment in ONE launch on the current stream (phx_vtrace,
+        include/phantom_amd_vtrace.h): the V-trace value targets and policy-gradient advantages of IMPALA / APPO (RLlib's
+        ``vtrace_torch.from_importance_weights``) for every (env instance, agent) column at once.  All tensors are ``[T, B, S]`` (or
+        ``[T, N]``) on the env's device: ``rewards`` f32 and ``truncations`` u8 as a rollout wrote them, ``vf_pred`` f32 = V(the
+        observation the policy acted on), ``behaviour_logp`` f32 = the rollout's ``action_logp``, ``target_logp`` f32 = the learner's
+        log-density of the same draws (the same tensor is allowed: on-policy), ``vf_next`` f32 = V(new_obs[t]), read only where a
+        trajectory is cut without terminating (a truncation, the fragment's last row; missing: 0), ``terminations`` u8 (missing: all
+        zero).  The importance ratio is exp of the log-ratio clamped to [-20, 20]; the three thresholds clip it for the TD term, the
+        trace and the advantage.  ``out``: the two f32 result tensors, 16-byte aligned (allocated here when None)."""
+        torch = _torch()
+        f32, u8 = torch.float32, torch.uint8
+        if rewards is None or rewards.dim() < 2:
+            raise ValueError("vtrace: `rewards` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(rewards.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"vtrace: `rewards` has shape {shape}: T and N must be >= 1")
+        if not (0.0 <= gamma <= 1.0 and 0.0 <= lambda_ <= 1.0):
+            raise ValueError(f"vtrace: gamma = {gamma} and lambda_ = {lambda_} must lie in [0, 1]")
+        clips = [float(np.float32(x)) for x in (clip_rho_threshold, clip_c_threshold, clip_pg_rho_threshold)]      # (as the struct holds them)
+        if not all(np.isfinite(x) and x > 0.0 for x in clips):
+            raise ValueError(f"vtrace: clip_rho_threshold = {clip_rho_threshold}, clip_c_threshold = {clip_c_threshold} and "
+                             f"clip_pg_rho_threshold = {clip_pg_rho_threshold} must be finite and > 0")
+        check_tensor("vtrace", "rewards", rewards, f32, shape, device=self.device)
+        check_tensor("vtrace", "truncations", truncations, u8, shape, device=self.device)
+        for name, x in (("vf_pred", vf_pred), ("behaviour_logp", behaviour_logp), ("target_logp", target_logp)):
+            check_tensor("vtrace", name, x, f32, shape, device=self.device)
+        for name, x, dtype in (("vf_next", vf_next, f32), ("terminations", terminations, u8)):
+            if x is not None:
+                check_tensor("vtrace", name, x, dtype, shape, device=self.device)
+        if out is None:
+            out = (torch.empty(shape, dtype=f32, device=self.device), torch.empty(shape, dtype=f32, device=self.device))
+        vs, pg = out
+        check_tensor("vtrace", "out[0]", vs, f32, shape, align=16, device=self.device)
+        check_tensor("vtrace", "out[1]", pg, f32, shape, align=16, device=self.device)
+        io = _abi.PhxVtraceIO(T=T, N=N, gamma=gamma, lambda_=lambda_, rho_bar=clips[0], c_bar=clips[1], pg_rho_bar=clips[2],
+                              reward=_ptr(rewards), vf_pred=_ptr(vf_pred), vf_next=_ptr(vf_next), behaviour_logp=_ptr(behaviour_logp),
+                              target_logp=_ptr(target_logp), terminated=_ptr(terminations), truncated=_ptr(truncations), vs=_ptr(vs),
+                              pg_advantage=_ptr(pg))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_vtrace(C.byref(io), self._stream()), "phx_vtrace")
+        return vs, pg
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

@@ -420,7 +420,7 @@ class PhantomEnv:
         return traj
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
-               gamma: float = 0.99, lambda_: float = 1.0):
+               gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0)):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -452,13 +452,30 @@ class PhantomEnv:
         Stackelberg env the critic sees +0.0 in place of ``obs`` rows where the agent holds no observation, ``vf_next`` at a piece's last
         row is the critic on the observation the agent holds there (``new_obs`` of the piece's latest row with ``new_obs_valid``, else
         the piece's first observation), and the launch is ``gae_masked``; without ``value_fn`` the same launch runs without value planes
-        (``lambda_ = 1``) for ``trajectory_rewards`` alone."""
+        (``lambda_ = 1``) for ``trajectory_rewards`` alone.
+
+        ``target_logp_fn``: an off-policy learner's batch (IMPALA, APPO).  A callable from (device f32 [M, D] ``obs``, device f32 [M]
+        raw actions) to f32 [M] or [M, 1]: the learner's CURRENT log-density of the recorded draws.  It is called once under
+        ``no_grad`` on all rows, in the row order ``value_fn`` sees, and needs ``policy``, ``explore=True`` and ``value_fn`` (the
+        behaviour log-density is the rollout's ``action_logp``); plain envs only.  ``vf_next`` is built as above and one
+        ``DeviceEnv.vtrace`` launch takes the place of the ``gae`` one, with ``vtrace_clip`` = RLlib's (clip_rho_threshold, the trace
+        clip 1.0, clip_pg_rho_threshold): the batch carries ``vf_preds`` / ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages``,
+        and ``advantages`` / ``value_targets`` stay None."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
             raise ValueError("sample: `policy` and replayed `actions` exclude each other")
         if explore and (policy is None or not policy.stochastic):
             raise ValueError("sample: explore=True needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
+        if target_logp_fn is not None:
+            if self.spec.env_type != _abi.ENV_PLAIN:
+                raise ValueError("sample: `target_logp_fn` serves plain envs only (an FSM / Stackelberg fragment has no device policy, "
+                                 "hence no behaviour log-density to correct)")
+            if policy is None or not explore or value_fn is None:
+                raise ValueError("sample: `target_logp_fn` needs `policy`, explore=True and `value_fn` (V-trace corrects the recorded "
+                                 "action_logp and bootstraps from the critic)")
+            if len(vtrace_clip) != 3:
+                raise ValueError("sample: `vtrace_clip` is (clip_rho_threshold, clip_c_threshold, clip_pg_rho_threshold)")
         dev = self._device()
         masked = self.spec.env_type != _abi.ENV_PLAIN            # per-agent trajectories with holes: validity planes, phx_gae_masked
         kinds = self.spec.kind[self.spec.strategic_idx]
@@ -540,8 +557,18 @@ class PhantomEnv:
                 ends = torch.as_tensor(piece_ends, device=dev.device)
                 vf_next = torch.zeros_like(vf)
                 vf_next[ends] = values(new_obs[ends])
-            adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
-            cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
+                if target_logp_fn is not None:
+                    tl = target_logp_fn(obs.reshape(-1, D), raw.reshape(-1))
+                    if tl.dtype != torch.float32 or tl.numel() != T * B * S:
+                        raise ValueError(f"sample: `target_logp_fn` must map (f32 [M, {D}], f32 [M]) to f32 [M] or [M, 1], got {tl.dtype} "
+                                         f"{tuple(tl.shape)}")
+                    tl = tl.detach().reshape(T, B, S).contiguous()
+            if target_logp_fn is not None:
+                vs, pg = dev.vtrace(rew, trunc, vf, logp, tl, vf_next, term, gamma, lambda_, *vtrace_clip)
+                cols.update(vf_preds=am(vf), target_logp=am(tl), vtrace_vs=am(vs), vtrace_pg_advantages=am(pg))
+            else:
+                adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
+                cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         elif masked:
             vf = vf_next = None
             if value_fn is not None:
@@ -572,7 +599,8 @@ class PhantomEnv:
                              never_finishes_alone=dev.never_terminates(), raw_actions=host.get("raw_actions"),
                              action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"), vf_preds=host.get("vf_preds"),
                              advantages=host.get("advantages"), value_targets=host.get("value_targets"),
-                             trajectory_rewards=host.get("trajectory_rewards"))
+                             trajectory_rewards=host.get("trajectory_rewards"), target_logp=host.get("target_logp"),
+                             vtrace_vs=host.get("vtrace_vs"), vtrace_pg_advantages=host.get("vtrace_pg_advantages"))
 
     def _noise_generator(self, device):
         """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""

@@ -409,15 +409,17 @@ class BatchedBaseEnv(_BaseEnvBase):
             self.env._dev = None                                   # a later call (try_restart / try_reset after stop) rebuilds the device env
 
     def sample(self, T: int, actions=None, exo=None, policy_mapping_fn=None, policy=None, explore: bool = False, generator=None,
-               value_fn=None, gamma: float = 0.99, lambda_: float = 1.0):
+               value_fn=None, gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0)):
         """The bulk exit: T steps of every env instance in fused device rollouts and the fragment as per-policy ``SampleBatch``
         column dicts (phantom_amd.rollout.FragmentBatch.to_sample_batches) -- no python object per (env, agent, step).
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
         ``generator``: on-policy sampling with a device policy, deterministic or exploring; ``value_fn`` / ``gamma`` / ``lambda_``: a critic, for the
         ``vf_preds`` / ``advantages`` / ``value_targets`` columns (PhantomEnv.sample).  On FSM and Stackelberg envs (shops, sellers, buyers)
-        the columns hold the rows where the agent acted, and ``rewards`` is what arrived until its next observation (``trajectory_rewards``)."""
+        the columns hold the rows where the agent acted, and ``rewards`` is what arrived until its next observation (``trajectory_rewards``).
+        ``target_logp_fn`` / ``vtrace_clip``: an IMPALA / APPO learner's batch -- ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages``
+        in place of ``advantages`` / ``value_targets`` (PhantomEnv.sample)."""
         return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
-                               lambda_=lambda_).to_sample_batches(policy_mapping_fn)
+                               lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip).to_sample_batches(policy_mapping_fn)
 
     def try_restart(self, env_id: Optional[int] = None) -> None:
         """RLlib calls this after a sub-env fault; the device env has no per-instance process to restart: reset it."""

@@ -169,6 +169,9 @@ class FragmentBatch:
     ``vf_preds`` f32 [B, S, T] V(obs)       ``advantages`` / ``value_targets`` f32 [B, S, T] (DeviceEnv.gae / gae_masked)
     ``trajectory_rewards`` f32 [B, S, T] or None (FSM / Stackelberg fragments of PhantomEnv.sample): at the rows where the agent
     acted, the sum of the rewards that arrived until its next observation (DeviceEnv.gae_masked); ``rewards`` stays step-aligned
+    an off-policy learner's fragment (PhantomEnv.sample(target_logp_fn=...)), else None -- ``advantages`` / ``value_targets`` are None then:
+    ``target_logp`` f32 [B, S, T] the learner's log-density of the recorded draws
+    ``vtrace_vs`` / ``vtrace_pg_advantages`` f32 [B, S, T] V-trace value targets and policy-gradient advantages (DeviceEnv.vtrace)
     """
 
     COLUMNS = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
@@ -176,7 +179,8 @@ class FragmentBatch:
     def __init__(self, agent_ids, obs, new_obs, actions, rewards, terminateds, truncateds, t, eps_id,
                  obs_valid=None, new_obs_valid=None, reward_valid=None, stage=None, stage_ids=None,
                  action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
-                 dist_inputs=None, vf_preds=None, advantages=None, value_targets=None, trajectory_rewards=None):
+                 dist_inputs=None, vf_preds=None, advantages=None, value_targets=None, trajectory_rewards=None, target_logp=None,
+                 vtrace_vs=None, vtrace_pg_advantages=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -188,6 +192,7 @@ class FragmentBatch:
         self.raw_actions, self.action_logp, self.dist_inputs = raw_actions, action_logp, dist_inputs
         self.vf_preds, self.advantages, self.value_targets = vf_preds, advantages, value_targets
         self.trajectory_rewards = trajectory_rewards
+        self.target_logp, self.vtrace_vs, self.vtrace_pg_advantages = target_logp, vtrace_vs, vtrace_pg_advantages
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
     # ---- RLlib-shaped exit -------------------------------------------------------------------------------------------
@@ -198,7 +203,8 @@ class FragmentBatch:
         out as reshaped VIEWS of the host arrays (no copy); envs whose dicts omit keys (FSM / Stackelberg) drop the rows of
         absent observations (boolean mask: a copy).  An exploring fragment's ``actions`` column is the raw draw z (what RLlib's
         sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``; a fragment with
-        ``vf_preds`` / ``advantages`` / ``value_targets`` has the columns of those names; a fragment with ``trajectory_rewards``
+        ``vf_preds`` / ``advantages`` / ``value_targets`` / ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages`` has the columns
+        of those names; a fragment with ``trajectory_rewards``
         takes its ``rewards`` column from them (an action's reward is what arrived until the agent's next observation)."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
@@ -229,7 +235,7 @@ class FragmentBatch:
                 cols["action_dist_inputs"] = sel(self.dist_inputs).reshape(B * n * T, -1)
             if self.trajectory_rewards is not None:
                 cols["rewards"] = sel(self.trajectory_rewards).reshape(-1)
-            for name in ("vf_preds", "advantages", "value_targets"):
+            for name in ("vf_preds", "advantages", "value_targets", "target_logp", "vtrace_vs", "vtrace_pg_advantages"):
                 if getattr(self, name) is not None:
                     cols[name] = sel(getattr(self, name)).reshape(-1)
             if self.obs_valid is not None:

@@ -9,7 +9,12 @@ per element of a flag plane, a plane counted only when it is given, vf_next coun
 --masked: phx_gae_masked_kernel at the same shapes, in the same process, alternating with phx_gae_kernel (the yardstick) under the same
 rotation and windows, every plane given, with two acted planes: all one (reward_valid all one: the result is phx_gae's, checked bit for
 bit) and alternating rows (an FSM supply chain: the shops act in even rows, their rewards arrive in odd rows and at an episode's end).
-It moves 28 B per element against phx_gae's 22 (two more flag bytes, one more f32 output): 1.27 is the expected ratio."""
+It moves 28 B per element against phx_gae's 22 (two more flag bytes, one more f32 output): 1.27 is the expected ratio.
+    python tools/gae_time.py --vtrace [--out profiles/vtrace_time.txt]          phx_vtrace against phx_gae and the torch loop
+--vtrace: phx_vtrace_kernel (include/phantom_amd_vtrace.h) with every plane given, at the same shapes, in the same process, alternating
+with two yardsticks under the same rotation and windows: phx_gae_kernel, and the torch reverse loop of V-trace written here (the per-row
+element-wise form of RLlib's from_importance_weights, with flags).  It first checks that the call with identical log-density planes
+equals phx_gae's value_target bit for bit.  It moves 30 B per element against phx_gae's 22 (two more f32 inputs): 1.36 is the expected ratio."""
 import argparse
 import ctypes as C
 import os
@@ -159,6 +164,104 @@ def measure_masked(lib, B, T, seconds, repeats, dev):
     return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, us=us)
 
 
+CLIP = (1.0, 1.0, 1.0)                                    # RLlib's defaults: clip_rho_threshold, the trace clip, clip_pg_rho_threshold
+
+
+def torch_vtrace_loop(b, vs, pg):
+    """V-trace with element-wise torch ops, one row at a time: from_importance_weights' reverse loop, cut at the flags"""
+    r, v, vn, bl, tl = b["reward"], b["vf_pred"], b["vf_next"], b["behaviour_logp"], b["target_logp"]
+    term, cut = b["terminated"].bool(), (b["terminated"] | b["truncated"]).bool()
+    T = r.shape[0]
+    zero = torch.zeros_like(r[0])
+    acc = zero
+    for t in range(T - 1, -1, -1):
+        rho = torch.exp(torch.clamp(tl[t] - bl[t], -20.0, 20.0))
+        if t == T - 1:
+            nv = nvs = torch.where(term[t], zero, vn[t])
+            c = zero
+        else:
+            nv = torch.where(term[t], zero, torch.where(cut[t], vn[t], v[t + 1]))
+            nvs = torch.where(term[t], zero, torch.where(cut[t], vn[t], vs[t + 1]))
+            c = torch.where(cut[t], zero, acc)
+        acc = torch.clamp(rho, max=CLIP[0]) * (r[t] + GAMMA * nv - v[t]) + (GAMMA * LAMBDA) * torch.clamp(rho, max=CLIP[1]) * c
+        vs[t] = acc + v[t]
+        pg[t] = torch.clamp(rho, max=CLIP[2]) * (r[t] + GAMMA * nvs - v[t])
+
+
+def measure_vtrace(lib, B, T, seconds, repeats, dev):
+    N = B * S
+    gen = torch.Generator(device=dev).manual_seed(0)
+    one = T * N * 30
+    n_sets = max(2, -(-(256 << 20) // one) + 1)           # working set beyond the 256 MiB Infinity Cache
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sets, gae, vt = [], [], []
+    for _ in range(n_sets):
+        b = buffer_set(T, N, dev, gen)
+        bl = torch.randn((T, N), generator=gen, device=dev) - 1.0
+        b.update(behaviour_logp=bl, target_logp=bl + 0.7 * torch.randn((T, N), generator=gen, device=dev),
+                 vs=torch.empty((T, N), device=dev), pg_advantage=torch.empty((T, N), device=dev))
+        sets.append(b)
+        gae.append(_abi.PhxGaeIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, **{k: b[k].data_ptr() for k in (
+            "reward", "vf_pred", "vf_next", "terminated", "truncated", "advantage", "value_target")}))
+        vt.append(_abi.PhxVtraceIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, rho_bar=CLIP[0], c_bar=CLIP[1], pg_rho_bar=CLIP[2], **{k: b[k].data_ptr() for k in (
+            "reward", "vf_pred", "vf_next", "behaviour_logp", "target_logp", "terminated", "truncated", "vs", "pg_advantage")}))
+
+    def caller(fn, ios):
+        refs = [C.byref(io) for io in ios]
+
+        def call(i):
+            if fn(refs[i % n_sets], stream) != 0:
+                raise RuntimeError(lib.phx_last_error().decode())
+        return call
+
+    vs_t, pg_t = torch.empty((T, N), device=dev), torch.empty((T, N), device=dev)
+    calls = {"phx_vtrace_kernel": caller(lib.phx_vtrace, vt), "phx_gae_kernel": caller(lib.phx_gae, gae),
+             "torch loop": lambda i: torch_vtrace_loop(sets[i % n_sets], vs_t, pg_t)}
+    b = sets[0]
+    # identical log-density planes (the same pointer): vs is phx_gae's value_target, bit for bit
+    same = _abi.PhxVtraceIO.from_buffer_copy(vt[0])
+    same.target_logp = same.behaviour_logp
+    if lib.phx_vtrace(C.byref(same), stream) != 0:
+        raise RuntimeError(lib.phx_last_error().decode())
+    calls["phx_gae_kernel"](0); torch.cuda.synchronize()
+    if not bool((b["vs"].view(torch.int32) == b["value_target"].view(torch.int32)).all()):
+        raise RuntimeError("phx_vtrace with identical log-density planes and phx_gae disagree")
+    calls["phx_vtrace_kernel"](0); calls["torch loop"](0); torch.cuda.synchronize()       # and the kernel agrees with the loop (a tolerance)
+    err = max(float((b["vs"] - vs_t).abs().max()), float((b["pg_advantage"] - pg_t).abs().max()))
+    if not err < 1e-3:
+        raise RuntimeError(f"kernel and torch loop disagree: max |diff| = {err}")
+    for fn in (calls["phx_vtrace_kernel"], calls["phx_gae_kernel"]):
+        for i in range(n_sets):
+            fn(i)
+    us = {k: [] for k in calls}
+    for _ in range(repeats):                              # alternating
+        for k, fn in calls.items():
+            us[k].append(window(fn, seconds)[0])
+    return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, us=us, max_abs_diff=err)
+
+
+def report_vtrace(rows):
+    out = ["phx_vtrace_kernel against phx_gae_kernel and the torch reverse loop of V-trace (tools/gae_time.py --vtrace); SC64 planes, N = 9 B columns,",
+           f"episodes of 100 steps, gamma = {GAMMA}, lambda = {LAMBDA}, thresholds {CLIP}, every plane given: 30 B per element moved against phx_gae's 22",
+           "(expected ratio 1.36).  One process, alternating, the same buffer rotation and windows.  Times: median [min .. max] over the repeats,",
+           "microseconds per call; spread = (max - min) / median.  With identical log-density planes vs equals phx_gae's value_target bit for bit",
+           "(checked before timing).",
+           f"device: {torch.cuda.get_device_name()}", ""]
+    for r in rows:
+        el = r["T"] * r["N"]
+        med = {k: float(np.median(v)) for k, v in r["us"].items()}
+        out.append(f"B = {r['B']:6d}  T = {r['T']:4d}  ({el / 1e6:.1f} M elements, {r['sets']} buffer sets of {r['set_mb']:.0f} MB; max |kernel - loop| = "
+                   f"{r['max_abs_diff']:.2e})")
+        for k, v in r["us"].items():
+            v = np.array(v)
+            m = med[k]
+            per = 22 if k == "phx_gae_kernel" else 30
+            out.append(f"    {k:20s} {m:10.1f} us  [{v.min():.1f} .. {v.max():.1f}]  spread {(v.max() - v.min()) / m:.3f}   {el * per / m / 1e6:.2f} TB/s"
+                       f" = {el * per / (m * 1e-6) / PEAK_BYTES_PER_S:.3f} of the peak"
+                       + ("" if k == "phx_vtrace_kernel" else f"   phx_vtrace_kernel takes {med['phx_vtrace_kernel'] / m:.4g} of this"))
+    return "\n".join(out) + "\n"
+
+
 def report_masked(rows):
     out = ["phx_gae_masked_kernel against phx_gae_kernel (tools/gae_time.py --masked); SC64 planes, N = 9 B columns, episodes of 100 steps,",
            f"gamma = {GAMMA}, lambda = {LAMBDA}, every plane given: 28 B per element moved against 22 (expected ratio 1.27).  One process, alternating,",
@@ -200,6 +303,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--masked", action="store_true", help="phx_gae_masked_kernel against phx_gae_kernel")
+    ap.add_argument("--vtrace", action="store_true", help="phx_vtrace_kernel against phx_gae_kernel and the torch loop of V-trace")
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
@@ -208,6 +312,14 @@ if __name__ == "__main__":
     lib = _abi.load_library()
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = []
+    if args.vtrace:
+        for B, T in SHAPES:
+            rows.append(measure_vtrace(lib, B, T, args.seconds, args.repeats, dev))
+            torch.cuda.empty_cache()
+            print(report_vtrace(rows[-1:]), flush=True)
+        with open(args.out or os.path.join(ROOT, "profiles", "vtrace_time.txt"), "w") as f:
+            f.write(report_vtrace(rows))
+        sys.exit(0)
     if args.masked:
         for B, T in SHAPES:
             rows.append(measure_masked(lib, B, T, args.seconds, args.repeats, dev))
