@@ -151,15 +151,25 @@ class PhxVtraceIO(C.Structure):
                                   "pg_advantage")]
 
 
+class PhxTrajNextIO(C.Structure):
+    """phx_traj_next_io (include/phantom_amd_traj.h): the planes of one phx_traj_next call"""
+    _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("N", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("truncated", "terminated", "acted", "new_obs_valid", "obs", "new_obs", "next_row", "next_terminated",
+                                  "next_truncated", "next_obs")]
+
+
 GAE_KERNEL = "phx_gae_kernel"
 GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
 VTRACE_KERNEL = "phx_vtrace_kernel"
+TRAJ_NEXT_KERNEL = "phx_traj_next_kernel"                # (with next_obs: + "+phx_traj_gather_kernel")
+TRAJ_GATHER_KERNEL = "phx_traj_gather_kernel"
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
 
 assert C.sizeof(PhxMsgRec) == 16
 assert C.sizeof(PhxVtraceIO) == 112      # (stated in include/phantom_amd_vtrace.h)
+assert C.sizeof(PhxTrajNextIO) == 96     # (stated in include/phantom_amd_traj.h)
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -266,6 +276,13 @@ def bind_vtrace(lib):
     return lib
 
 
+def bind_traj(lib):
+    """restype / argtypes of include/phantom_amd_traj.h's entry point: libphantom_amd.so only, like bind_vtrace"""
+    lib.phx_traj_next.restype = C.c_int32
+    lib.phx_traj_next.argtypes = [C.POINTER(PhxTrajNextIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -283,6 +300,7 @@ def load_library():
     bind_signatures(lib)
     bind_gae(lib)
     bind_vtrace(lib)
+    bind_traj(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -776,6 +776,62 @@ class DeviceEnv:
             self._check(self.lib.phx_vtrace(C.byref(io), self._stream()), "phx_vtrace")
         return vs, pg
 
+    def traj_next(self, truncations, terminations=None, acted=None, new_obs_valid=None, obs=None, new_obs=None, out=None):
+        """``(next_row, next_terminated, next_truncated, next_obs or None)`` of a time-major fragment whose per-agent trajectories have
+        holes (FSM / Stackelberg envs), on the current stream (phx_traj_next, include/phantom_amd_traj.h): what a learner that reads
+        one agent's transitions needs next to ``gae_masked``'s ``trajectory_rewards``, over the same segments.  The flag planes are
+        ``[T, B, S]`` (or ``[T, N]``) u8 on the env's device: ``truncations`` / ``terminations`` as a rollout wrote them (slices of
+        longer recordings are fine), ``acted`` (!= 0: a trajectory row, as in ``gae_masked``) and ``new_obs_valid`` (the rollout's
+        ``obs_valid`` plane: != 0, step t returned an observation to the agent); a missing ``terminations`` reads as all zero, a
+        missing ``acted`` or ``new_obs_valid`` as all one.  At a trajectory row ``next_row`` (i32) is the latest row of the agent's
+        segment -- up to its next trajectory row or the first done flag, whichever comes first -- whose ``new_obs`` the agent received
+        (-1: none, it still holds ``obs`` of the row itself), and the two u8 flags are those of the row that closed the segment
+        (terminated wins over truncated; the fragment's last row without a flag sets neither).  With ``obs`` and ``new_obs`` (f32
+        ``[T, B, S, D]``, D <= 64; both or neither) a second launch gathers ``next_obs`` = ``new_obs[next_row]``, or ``obs`` of the
+        row itself where ``next_row`` is -1, bit for bit.  Rows that are no trajectory rows hold -1, 0, 0 and +0.0.  A trajectory row
+        is a complete transition iff one of its flags is set or ``next_row >= 0``.  ``out``: the four result tensors (the last one
+        None without ``obs``), 16-byte aligned (allocated here when None)."""
+        torch = _torch()
+        f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+        if truncations is None or not hasattr(truncations, "dim") or truncations.dim() < 2:
+            raise ValueError("traj_next: `truncations` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(truncations.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"traj_next: `truncations` has shape {shape}: T and N must be >= 1")
+        check_tensor("traj_next", "truncations", truncations, u8, shape, device=self.device)
+        for name, x in (("terminations", terminations), ("acted", acted), ("new_obs_valid", new_obs_valid)):
+            if x is not None:
+                check_tensor("traj_next", name, x, u8, shape, device=self.device)
+        if (obs is None) != (new_obs is None):
+            raise ValueError("traj_next: `obs` and `new_obs` come together (both for `next_obs`, neither without it)")
+        gather, D = obs is not None, 0
+        if gather:
+            if not hasattr(obs, "dim") or obs.dim() != len(shape) + 1 or not 1 <= obs.shape[-1] <= 64:
+                raise ValueError(f"traj_next: `obs` must be a {shape + ('D',)} tensor with 1 <= D <= 64")
+            D = int(obs.shape[-1])
+            check_tensor("traj_next", "obs", obs, f32, shape + (D,), device=self.device)
+            check_tensor("traj_next", "new_obs", new_obs, f32, shape + (D,), device=self.device)
+        if out is None:
+            e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+            out = (e(shape, i32), e(shape, u8), e(shape, u8), e(shape + (D,), f32) if gather else None)
+        if len(out) != 4:
+            raise ValueError("traj_next: `out` is (next_row, next_terminated, next_truncated, next_obs or None)")
+        nr, nte, ntr, nob = out
+        check_tensor("traj_next", "out[0]", nr, i32, shape, align=16, device=self.device)
+        check_tensor("traj_next", "out[1]", nte, u8, shape, align=16, device=self.device)
+        check_tensor("traj_next", "out[2]", ntr, u8, shape, align=16, device=self.device)
+        if gather:
+            check_tensor("traj_next", "out[3]", nob, f32, shape + (D,), align=16, device=self.device)
+        elif nob is not None:
+            raise ValueError("traj_next: `out[3]` (next_obs) needs `obs` and `new_obs`")
+        io = _abi.PhxTrajNextIO(T=T, D=D, N=N, truncated=_ptr(truncations), terminated=_ptr(terminations), acted=_ptr(acted),
+                                new_obs_valid=_ptr(new_obs_valid), obs=_ptr(obs), new_obs=_ptr(new_obs), next_row=_ptr(nr),
+                                next_terminated=_ptr(nte), next_truncated=_ptr(ntr), next_obs=_ptr(nob))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_traj_next(C.byref(io), self._stream()), "phx_traj_next")
+        return nr, nte, ntr, nob
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

@@ -436,7 +436,12 @@ class PhantomEnv:
         ``reset()`` / ``step`` / ``sample()`` left at the first row, ``reset()``'s at an episode's first row, ``new_obs_valid[t - 1]``
         elsewhere.  One ``DeviceEnv.gae_masked`` launch gives ``trajectory_rewards`` -- at the rows where an agent acted, the sum of the
         rewards that arrived until its next observation (the reference hands a reward over with the NEXT observation; ``rewards`` stays
-        step-aligned) -- which ``to_sample_batches()`` takes as its ``rewards`` column.  ``stage`` / ``stage_ids`` come from the host's
+        step-aligned) -- which ``to_sample_batches()`` takes as its ``rewards`` column.  One ``DeviceEnv.traj_next`` call before it gives the
+        other three columns of the agent's transition over the same segments -- ``trajectory_new_obs`` (the agent's NEXT observation),
+        ``trajectory_terminateds`` / ``trajectory_truncateds`` (the flags of the step that ended the transition, also where the agent
+        did not act in that step) and ``trajectory_next_row`` -- which ``to_sample_batches()`` takes as ``new_obs`` / ``terminateds`` /
+        ``truncateds``; ``new_obs`` / ``terminateds`` / ``truncateds`` of the batch stay step-aligned.  A kept row is a complete transition
+        iff it carries a flag or ``trajectory_next_row >= 0`` (only an agent's last row of the fragment can be incomplete).  ``stage`` / ``stage_ids`` come from the host's
         own transition table; an env with rule-form stage handlers, whose transitions depend on agent state, gets ``stage = None``.
 
         ``policy``: an ``MLPPolicy`` evaluated on the device (on-policy sampling, plain supply chains only: ValueError otherwise); ``explore=True`` samples its
@@ -570,6 +575,10 @@ class PhantomEnv:
                 adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         elif masked:
+            # the agent's own view of the other three transition columns, over gae_masked's segments (before it: last_kernel() stays its)
+            nrow, nterm, ntrunc, nobs = dev.traj_next(trunc, term, acted, nvalid, obs, new_obs)
+            cols.update(trajectory_next_row=am(nrow), trajectory_new_obs=am(nobs), trajectory_terminateds=am(nterm),
+                        trajectory_truncateds=am(ntrunc))
             vf = vf_next = None
             if value_fn is not None:
                 with torch.no_grad():
@@ -591,6 +600,7 @@ class PhantomEnv:
         host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         stage = np.concatenate(stages, axis=1) if stages and all(x is not None for x in stages) else None
+        tbool = lambda k: host[k].astype(bool) if k in host else None
         return FragmentBatch(ids, host["obs"], host["new_obs"], host["actions"], host["rewards"], host["terminateds"].astype(bool),
                              host["truncateds"].astype(bool), np.broadcast_to(t_in_ep, (B, T)).copy(),
                              (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64),
@@ -600,7 +610,9 @@ class PhantomEnv:
                              action_logp=host.get("action_logp"), dist_inputs=host.get("dist_inputs"), vf_preds=host.get("vf_preds"),
                              advantages=host.get("advantages"), value_targets=host.get("value_targets"),
                              trajectory_rewards=host.get("trajectory_rewards"), target_logp=host.get("target_logp"),
-                             vtrace_vs=host.get("vtrace_vs"), vtrace_pg_advantages=host.get("vtrace_pg_advantages"))
+                             vtrace_vs=host.get("vtrace_vs"), vtrace_pg_advantages=host.get("vtrace_pg_advantages"),
+                             trajectory_next_row=host.get("trajectory_next_row"), trajectory_new_obs=host.get("trajectory_new_obs"),
+                             trajectory_terminateds=tbool("trajectory_terminateds"), trajectory_truncateds=tbool("trajectory_truncateds"))
 
     def _noise_generator(self, device):
         """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""

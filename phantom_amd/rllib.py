@@ -415,7 +415,9 @@ class BatchedBaseEnv(_BaseEnvBase):
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
         ``generator``: on-policy sampling with a device policy, deterministic or exploring; ``value_fn`` / ``gamma`` / ``lambda_``: a critic, for the
         ``vf_preds`` / ``advantages`` / ``value_targets`` columns (PhantomEnv.sample).  On FSM and Stackelberg envs (shops, sellers, buyers)
-        the columns hold the rows where the agent acted, and ``rewards`` is what arrived until its next observation (``trajectory_rewards``).
+        the columns hold the rows where the agent acted, and ``rewards`` is what arrived until its next observation (``trajectory_rewards``);
+        ``new_obs`` / ``terminateds`` / ``truncateds`` are the agent's next observation and the flags of the step that ended its transition
+        (``trajectory_new_obs`` / ``trajectory_terminateds`` / ``trajectory_truncateds``), next to a ``trajectory_next_row`` column.
         ``target_logp_fn`` / ``vtrace_clip``: an IMPALA / APPO learner's batch -- ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages``
         in place of ``advantages`` / ``value_targets`` (PhantomEnv.sample)."""
         return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,

@@ -169,6 +169,12 @@ class FragmentBatch:
     ``vf_preds`` f32 [B, S, T] V(obs)       ``advantages`` / ``value_targets`` f32 [B, S, T] (DeviceEnv.gae / gae_masked)
     ``trajectory_rewards`` f32 [B, S, T] or None (FSM / Stackelberg fragments of PhantomEnv.sample): at the rows where the agent
     acted, the sum of the rewards that arrived until its next observation (DeviceEnv.gae_masked); ``rewards`` stays step-aligned
+    ``trajectory_next_row`` i32 [B, S, T], ``trajectory_new_obs`` f32 [B, S, T, D], ``trajectory_terminateds`` / ``trajectory_truncateds``
+    bool [B, S, T], or None (FSM / Stackelberg fragments of PhantomEnv.sample; DeviceEnv.traj_next): at the rows where the agent acted,
+    the fragment row whose ``new_obs`` it holds when its transition ends (-1: none, it still holds ``obs``), that observation, and the done
+    flags of the step that ended the transition; -1 / +0.0 / False elsewhere.  ``new_obs`` / ``terminateds`` / ``truncateds`` stay
+    step-aligned.  A kept row is a COMPLETE transition iff it carries a flag or ``trajectory_next_row >= 0``; the one row that can be
+    incomplete is the (env instance, agent)'s last trajectory row of the fragment -- its answer lies in the next fragment
     an off-policy learner's fragment (PhantomEnv.sample(target_logp_fn=...)), else None -- ``advantages`` / ``value_targets`` are None then:
     ``target_logp`` f32 [B, S, T] the learner's log-density of the recorded draws
     ``vtrace_vs`` / ``vtrace_pg_advantages`` f32 [B, S, T] V-trace value targets and policy-gradient advantages (DeviceEnv.vtrace)
@@ -180,7 +186,8 @@ class FragmentBatch:
                  obs_valid=None, new_obs_valid=None, reward_valid=None, stage=None, stage_ids=None,
                  action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
                  dist_inputs=None, vf_preds=None, advantages=None, value_targets=None, trajectory_rewards=None, target_logp=None,
-                 vtrace_vs=None, vtrace_pg_advantages=None):
+                 vtrace_vs=None, vtrace_pg_advantages=None, trajectory_next_row=None, trajectory_new_obs=None,
+                 trajectory_terminateds=None, trajectory_truncateds=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -192,6 +199,8 @@ class FragmentBatch:
         self.raw_actions, self.action_logp, self.dist_inputs = raw_actions, action_logp, dist_inputs
         self.vf_preds, self.advantages, self.value_targets = vf_preds, advantages, value_targets
         self.trajectory_rewards = trajectory_rewards
+        self.trajectory_next_row, self.trajectory_new_obs = trajectory_next_row, trajectory_new_obs
+        self.trajectory_terminateds, self.trajectory_truncateds = trajectory_terminateds, trajectory_truncateds
         self.target_logp, self.vtrace_vs, self.vtrace_pg_advantages = target_logp, vtrace_vs, vtrace_pg_advantages
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
@@ -205,7 +214,11 @@ class FragmentBatch:
         sampler records), next to ``action_logp``, ``action_prob`` = exp(action_logp) and ``action_dist_inputs``; a fragment with
         ``vf_preds`` / ``advantages`` / ``value_targets`` / ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages`` has the columns
         of those names; a fragment with ``trajectory_rewards``
-        takes its ``rewards`` column from them (an action's reward is what arrived until the agent's next observation)."""
+        takes its ``rewards`` column from them (an action's reward is what arrived until the agent's next observation), and one with
+        ``trajectory_new_obs`` / ``trajectory_terminateds`` / ``trajectory_truncateds`` its ``new_obs`` / ``terminateds`` / ``truncateds``
+        columns from those (the agent's next observation and the flags of the step that ended its transition), plus a
+        ``trajectory_next_row`` column: a row is a complete transition iff it carries a flag or ``trajectory_next_row >= 0`` (only an
+        agent's last row of the fragment can be incomplete)."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
         for s, aid in enumerate(self.agent_ids):
@@ -235,6 +248,14 @@ class FragmentBatch:
                 cols["action_dist_inputs"] = sel(self.dist_inputs).reshape(B * n * T, -1)
             if self.trajectory_rewards is not None:
                 cols["rewards"] = sel(self.trajectory_rewards).reshape(-1)
+            if self.trajectory_new_obs is not None:
+                cols["new_obs"] = sel(self.trajectory_new_obs).reshape(B * n * T, -1)
+            if self.trajectory_terminateds is not None:
+                cols["terminateds"] = sel(self.trajectory_terminateds).reshape(-1)
+            if self.trajectory_truncateds is not None:
+                cols["truncateds"] = sel(self.trajectory_truncateds).reshape(-1)
+            if self.trajectory_next_row is not None:
+                cols["trajectory_next_row"] = sel(self.trajectory_next_row).reshape(-1)
             for name in ("vf_preds", "advantages", "value_targets", "target_logp", "vtrace_vs", "vtrace_pg_advantages"):
                 if getattr(self, name) is not None:
                     cols[name] = sel(getattr(self, name)).reshape(-1)

@@ -14,7 +14,15 @@ It moves 28 B per element against phx_gae's 22 (two more flag bytes, one more f3
 --vtrace: phx_vtrace_kernel (include/phantom_amd_vtrace.h) with every plane given, at the same shapes, in the same process, alternating
 with two yardsticks under the same rotation and windows: phx_gae_kernel, and the torch reverse loop of V-trace written here (the per-row
 element-wise form of RLlib's from_importance_weights, with flags).  It first checks that the call with identical log-density planes
-equals phx_gae's value_target bit for bit.  It moves 30 B per element against phx_gae's 22 (two more f32 inputs): 1.36 is the expected ratio."""
+equals phx_gae's value_target bit for bit.  It moves 30 B per element against phx_gae's 22 (two more f32 inputs): 1.36 is the expected ratio.
+    python tools/gae_time.py --traj [--out profiles/traj_next_time.txt]         phx_traj_next against phx_gae_masked and torch
+--traj: phx_traj_next (include/phantom_amd_traj.h) at the same shapes with D = 3 and an FSM supply chain's planes (the shops act in even
+rows and receive an observation from odd rows), every flag plane given, without and with next_obs, in the same process, alternating with
+two yardsticks under the same rotation and windows: phx_gae_masked_kernel (unchanged), and the same result written in torch here (the
+per-row reverse loop of selects, plus one torch.gather for next_obs).  It first checks the reduction case (no acted, no new_obs_valid:
+next_row[t] == t, the step's own flags, next_obs == new_obs bit for bit) and that kernel and torch agree on every output.  Expectation: the
+scan moves 10 B per element (four flag bytes in, six bytes out), the gather 5 + 8 D B per element that the result needs (acted, next_row,
+one source word and one stored word per word; loading both candidate sources, as the kernel does, reads up to 4 D B more)."""
 import argparse
 import ctypes as C
 import os
@@ -240,6 +248,134 @@ def measure_vtrace(lib, B, T, seconds, repeats, dev):
     return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, us=us, max_abs_diff=err)
 
 
+TRAJ_D = 3
+
+
+def torch_traj_next(b, out, gather):
+    """phx_traj_next with element-wise torch ops, one row at a time (the header's scan), and one torch.gather for next_obs"""
+    tr, te, ac, nv = (b[k] != 0 for k in ("truncated", "terminated", "acted", "new_obs_valid"))
+    T, N = tr.shape
+    nr = torch.full((N,), -1, dtype=torch.int32, device=tr.device)
+    term = torch.zeros((N,), dtype=torch.bool, device=tr.device)
+    trunc = torch.zeros_like(term)
+    minus, no = torch.full_like(nr, -1), torch.zeros_like(term)
+    for t in range(T - 1, -1, -1):
+        c = te[t] | tr[t] if t < T - 1 else torch.ones_like(term)
+        here = torch.where(nv[t], torch.full_like(nr, t), minus)
+        nr = torch.where(c, here, torch.where(nr < 0, here, nr))
+        term = torch.where(c, te[t], term)
+        trunc = torch.where(c, ~te[t] & tr[t], trunc)
+        a = ac[t]
+        out["next_row"][t] = torch.where(a, nr, minus)
+        out["next_terminated"][t] = a & term
+        out["next_truncated"][t] = a & trunc
+        nr, term, trunc = torch.where(a, minus, nr), torch.where(a, no, term), torch.where(a, no, trunc)
+    if gather:
+        row = out["next_row"].to(torch.int64)
+        src = b["new_obs"].gather(0, row.clamp(min=0)[..., None].expand(T, N, TRAJ_D))
+        held = torch.where((row >= 0)[..., None], src, b["obs"])
+        torch.where(ac[..., None], held, torch.zeros((), device=tr.device), out=out["next_obs"])
+
+
+def measure_traj(lib, B, T, seconds, repeats, dev):
+    N, D = B * S, TRAJ_D
+    gen = torch.Generator(device=dev).manual_seed(0)
+    one = T * N * (10 + 12 * D)
+    n_sets = max(2, -(-(256 << 20) // (T * N * 10)) + 1)   # the scan's own planes alone exceed the 256 MiB Infinity Cache
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    u8 = lambda: torch.zeros((T, N), dtype=torch.uint8, device=dev)
+    sets, scan, both, masked = [], [], [], []
+    for _ in range(n_sets):
+        b = buffer_set(T, N, dev, gen)                   # (reward, value planes, flags, advantage, value_target: the yardstick's)
+        acted, nvalid, rv = u8(), u8(), u8()
+        acted[0::2] = 1
+        nvalid[1::2] = 1; nvalid[EPISODE - 1::EPISODE] = 1
+        rv[1::2] = 1; rv[EPISODE - 1::EPISODE] = 1
+        b.update(acted=acted, new_obs_valid=nvalid, reward_valid=rv, reward_sum=torch.empty((T, N), device=dev),
+                 obs=torch.randn((T, N, D), generator=gen, device=dev), new_obs=torch.randn((T, N, D), generator=gen, device=dev),
+                 next_row=torch.empty((T, N), dtype=torch.int32, device=dev), next_terminated=u8(), next_truncated=u8(),
+                 next_obs=torch.empty((T, N, D), device=dev))
+        sets.append(b)
+        p = lambda *ks: {k: b[k].data_ptr() for k in ks}
+        flags = ("truncated", "terminated", "acted", "new_obs_valid", "next_row", "next_terminated", "next_truncated")
+        scan.append(_abi.PhxTrajNextIO(T=T, D=D, N=N, **p(*flags)))
+        both.append(_abi.PhxTrajNextIO(T=T, D=D, N=N, **p(*flags, "obs", "new_obs", "next_obs")))
+        masked.append(_abi.PhxGaeMaskedIO(T=T, N=N, gamma=GAMMA, lambda_=LAMBDA, **p("reward", "vf_pred", "vf_next", "terminated", "truncated", "acted",
+                                                                                      "reward_valid", "advantage", "value_target", "reward_sum")))
+
+    def caller(fn, ios):
+        refs = [C.byref(io) for io in ios]
+
+        def call(i):
+            if fn(refs[i % n_sets], stream) != 0:
+                raise RuntimeError(lib.phx_last_error().decode())
+        return call
+
+    t_out = dict(next_row=torch.empty((T, N), dtype=torch.int32, device=dev), next_terminated=u8(), next_truncated=u8(),
+                 next_obs=torch.empty((T, N, D), device=dev))
+    calls = {"phx_traj_next, scan alone": caller(lib.phx_traj_next, scan), "phx_traj_next, scan + gather": caller(lib.phx_traj_next, both),
+             "phx_gae_masked_kernel": caller(lib.phx_gae_masked, masked),
+             "torch, scan alone": lambda i: torch_traj_next(sets[i % n_sets], t_out, False),
+             "torch, scan + gather": lambda i: torch_traj_next(sets[i % n_sets], t_out, True)}
+    b = sets[0]
+    # the reduction case: no acted, no new_obs_valid
+    red = _abi.PhxTrajNextIO.from_buffer_copy(both[0])
+    red.acted = red.new_obs_valid = None
+    if lib.phx_traj_next(C.byref(red), stream) != 0:
+        raise RuntimeError(lib.phx_last_error().decode())
+    torch.cuda.synchronize()
+    te, tr = b["terminated"] != 0, b["truncated"] != 0
+    ok = (bool((b["next_row"] == torch.arange(T, dtype=torch.int32, device=dev)[:, None]).all()) and bool(((b["next_terminated"] != 0) == te).all())
+          and bool(((b["next_truncated"] != 0) == (~te & tr)).all())
+          and bool((b["next_obs"].view(torch.int32) == b["new_obs"].view(torch.int32)).all()))
+    if not ok:
+        raise RuntimeError("phx_traj_next: the reduction case does not hold")
+    calls["phx_traj_next, scan + gather"](0); calls["torch, scan + gather"](0); torch.cuda.synchronize()
+    for k in ("next_row", "next_terminated", "next_truncated"):
+        if not bool((b[k] == t_out[k]).all()):
+            raise RuntimeError(f"kernel and torch disagree on {k}")
+    if not bool((b["next_obs"].view(torch.int32) == t_out["next_obs"].view(torch.int32)).all()):
+        raise RuntimeError("kernel and torch disagree on next_obs")
+    for k in list(calls)[:3]:
+        for i in range(n_sets):
+            calls[k](i)
+    us = {k: [] for k in calls}
+    for _ in range(repeats):                              # alternating
+        for k, fn in calls.items():
+            us[k].append(window(fn, seconds)[0])
+    return dict(B=B, T=T, N=N, sets=n_sets, set_mb=one / 1e6, us=us)
+
+
+def report_traj(rows):
+    D = TRAJ_D
+    per = {"phx_traj_next, scan alone": 10, "phx_traj_next, scan + gather": 10 + 5 + 8 * D, "phx_gae_masked_kernel": 28,
+           "torch, scan alone": 10, "torch, scan + gather": 10 + 5 + 8 * D}
+    out = ["phx_traj_next against phx_gae_masked_kernel and the same result in torch (tools/gae_time.py --traj); SC64 planes, N = 9 B columns,",
+           f"episodes of 100 steps, D = {D}, an FSM supply chain's acted / new_obs_valid planes (even rows / odd rows), every flag plane given.",
+           f"Expected bytes per element: the scan 10 (four flag bytes in, six out), the gather 5 + 8 D = {5 + 8 * D}, phx_gae_masked 28.  One process,",
+           "alternating, the same buffer rotation and windows.  Times: median [min .. max] over the repeats, microseconds per call; spread =",
+           "(max - min) / median; TB/s = the expected bytes over the median.  The reduction case and kernel == torch on all four outputs are",
+           "checked before timing.",
+           f"device: {torch.cuda.get_device_name()}", ""]
+    for r in rows:
+        el = r["T"] * r["N"]
+        med = {k: float(np.median(v)) for k, v in r["us"].items()}
+        out.append(f"B = {r['B']:6d}  T = {r['T']:4d}  ({el / 1e6:.1f} M elements, {r['sets']} buffer sets of {r['set_mb']:.0f} MB)")
+        for k, v in r["us"].items():
+            v = np.array(v)
+            m = med[k]
+            line = (f"    {k:30s} {m:10.1f} us  [{v.min():.1f} .. {v.max():.1f}]  spread {(v.max() - v.min()) / m:.3f}   {el * per[k] / m / 1e6:.2f} TB/s"
+                    f" = {el * per[k] / (m * 1e-6) / PEAK_BYTES_PER_S:.3f} of the peak")
+            if k == "phx_gae_masked_kernel":
+                line += f"   scan alone takes {med['phx_traj_next, scan alone'] / m:.3f} of this (expected 10 / 28 = 0.357)"
+            if k.startswith("torch"):
+                line += f"   ratio to the kernel {m / med[k.replace('torch', 'phx_traj_next')]:.1f}x"
+            out.append(line)
+        g = med["phx_traj_next, scan + gather"] - med["phx_traj_next, scan alone"]
+        out.append(f"    the gather by difference        {g:10.1f} us   {el * (5 + 8 * D) / g / 1e6:.2f} TB/s of its expected {5 + 8 * D} B per element")
+    return "\n".join(out) + "\n"
+
+
 def report_vtrace(rows):
     out = ["phx_vtrace_kernel against phx_gae_kernel and the torch reverse loop of V-trace (tools/gae_time.py --vtrace); SC64 planes, N = 9 B columns,",
            f"episodes of 100 steps, gamma = {GAMMA}, lambda = {LAMBDA}, thresholds {CLIP}, every plane given: 30 B per element moved against phx_gae's 22",
@@ -304,6 +440,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--masked", action="store_true", help="phx_gae_masked_kernel against phx_gae_kernel")
     ap.add_argument("--vtrace", action="store_true", help="phx_vtrace_kernel against phx_gae_kernel and the torch loop of V-trace")
+    ap.add_argument("--traj", action="store_true", help="phx_traj_next against phx_gae_masked_kernel and the same result in torch")
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
@@ -312,6 +449,14 @@ if __name__ == "__main__":
     lib = _abi.load_library()
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = []
+    if args.traj:
+        for B, T in SHAPES:
+            rows.append(measure_traj(lib, B, T, args.seconds, args.repeats, dev))
+            torch.cuda.empty_cache()
+            print(report_traj(rows[-1:]), flush=True)
+        with open(args.out or os.path.join(ROOT, "profiles", "traj_next_time.txt"), "w") as f:
+            f.write(report_traj(rows))
+        sys.exit(0)
     if args.vtrace:
         for B, T in SHAPES:
             rows.append(measure_vtrace(lib, B, T, args.seconds, args.repeats, dev))
