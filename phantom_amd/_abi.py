@@ -158,11 +158,29 @@ class PhxTrajNextIO(C.Structure):
                                   "next_truncated", "next_obs")]
 
 
+COMPACT_MAX_PLANES = 16
+
+
+class PhxCompactPlane(C.Structure):
+    """phx_compact_plane (include/phantom_amd_compact.h): one plane of a phx_traj_compact call"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("elem_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PhxTrajCompactIO(C.Structure):
+    """phx_traj_compact_io (include/phantom_amd_compact.h): the planes of one phx_traj_compact call"""
+    _fields_ = [("T", C.c_int32), ("n_planes", C.c_int32), ("N", C.c_int64), ("capacity", C.c_int64), ("keep", C.c_void_p),
+                ("start", C.c_void_p), ("out_row", C.c_void_p), ("out_col", C.c_void_p), ("plane", PhxCompactPlane * COMPACT_MAX_PLANES)]
+
+
 GAE_KERNEL = "phx_gae_kernel"
 GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
 VTRACE_KERNEL = "phx_vtrace_kernel"
 TRAJ_NEXT_KERNEL = "phx_traj_next_kernel"                # (with next_obs: + "+phx_traj_gather_kernel")
 TRAJ_GATHER_KERNEL = "phx_traj_gather_kernel"
+COMPACT_COUNT_KERNEL = "phx_compact_count_kernel"        # (phx_traj_compact: the three names joined by "+"; the scatter's is missing
+COMPACT_SCAN_KERNEL = "phx_compact_scan_kernel"          #  where it has nothing to write)
+COMPACT_SCATTER_KERNEL = "phx_compact_scatter_kernel"
+COMPACT_KERNELS = "+".join((COMPACT_COUNT_KERNEL, COMPACT_SCAN_KERNEL, COMPACT_SCATTER_KERNEL))
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -170,6 +188,7 @@ RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 assert C.sizeof(PhxMsgRec) == 16
 assert C.sizeof(PhxVtraceIO) == 112      # (stated in include/phantom_amd_vtrace.h)
 assert C.sizeof(PhxTrajNextIO) == 96     # (stated in include/phantom_amd_traj.h)
+assert C.sizeof(PhxCompactPlane) == 24 and C.sizeof(PhxTrajCompactIO) == 440      # (stated in include/phantom_amd_compact.h)
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -283,6 +302,13 @@ def bind_traj(lib):
     return lib
 
 
+def bind_compact(lib):
+    """restype / argtypes of include/phantom_amd_compact.h's entry point: libphantom_amd.so only, like bind_traj"""
+    lib.phx_traj_compact.restype = C.c_int32
+    lib.phx_traj_compact.argtypes = [C.POINTER(PhxTrajCompactIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -301,6 +327,7 @@ def load_library():
     bind_gae(lib)
     bind_vtrace(lib)
     bind_traj(lib)
+    bind_compact(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -832,6 +832,64 @@ class DeviceEnv:
             self._check(self.lib.phx_traj_next(C.byref(io), self._stream()), "phx_traj_next")
         return nr, nte, ntr, nob
 
+    def compact(self, keep, planes, capacity=None, out=None):
+        """``(start, out_row, out_col, {name: dense tensor})``: the kept elements of time-major planes, dense and in (column, row) =
+        (env instance, agent, step) order, on the current stream (phx_traj_compact, include/phantom_amd_compact.h) -- the hole rows of
+        an FSM / Stackelberg fragment dropped on the device, fused with the transpose ``to_sample_batches()``'s row order needs.
+        ``keep`` is u8 ``[T, B, S]`` (or ``[T, N]``), != 0 keeps the element; ``planes`` maps a name to a tensor ``[T, N..]`` (u8, f32,
+        i32) or ``[T, N.., w]`` (f32, i32; w <= 64) on the env's device -- slices of longer recordings are fine.  ``start`` i64
+        ``[N + 1]`` holds every column's first position and, in ``start[N]``, the number K of kept elements; ``out_row`` / ``out_col``
+        i32 ``[capacity]`` the row and column of every position; a dense tensor is ``[capacity]`` or ``[capacity, w]``.  Only the first
+        ``min(K, capacity)`` elements of them are written (``capacity`` defaults to T * N: everything fits), the caller reads K from
+        ``start[N]`` -- the call does not synchronise.  ``out``: the same four, caller-owned and 16-byte aligned (``out_row`` /
+        ``out_col`` may be None there: not written); allocated here when None.  More than 16 planes are served by further launches of
+        up to 16 planes each, and each of them counts and scans ``keep`` again (T * N bytes read and one scan of N + 1 entries)."""
+        torch = _torch()
+        f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
+        if keep is None or not hasattr(keep, "dim") or keep.dim() < 2:
+            raise ValueError("compact: `keep` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(keep.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"compact: `keep` has shape {shape}: T and N must be >= 1")
+        check_tensor("compact", "keep", keep, u8, shape, device=self.device)
+        capacity = T * N if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"compact: capacity = {capacity} must be >= 0")
+        planes = dict(planes)
+        words = {}
+        for name, x in planes.items():
+            if x is None or not hasattr(x, "dim") or x.dim() not in (len(shape), len(shape) + 1):
+                raise ValueError(f"compact: plane `{name}` must be a {shape} or {shape + ('w',)} tensor")
+            tail = tuple(x.shape[len(shape):])
+            if tail and (x.dtype == u8 or not 1 <= tail[0] <= 64):
+                raise ValueError(f"compact: plane `{name}`: a trailing axis needs f32 or i32 and 1 <= w <= 64")
+            check_tensor("compact", f"plane `{name}`", x, (u8, f32, i32), shape + tail, device=self.device)
+            words[name] = tail
+        e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+        if out is None:
+            out = (e((N + 1,), i64), e((capacity,), i32), e((capacity,), i32), {k: e((capacity,) + words[k], x.dtype) for k, x in planes.items()})
+        if len(out) != 4 or set(out[3]) != set(planes):
+            raise ValueError("compact: `out` is (start, out_row or None, out_col or None, {name: dense tensor}) with the planes' names")
+        start, orow, ocol, dense = out
+        check_tensor("compact", "out[0]", start, i64, (N + 1,), align=16, device=self.device)
+        for i, x in ((1, orow), (2, ocol)):
+            if x is not None:
+                check_tensor("compact", f"out[{i}]", x, i32, (capacity,), align=16, device=self.device)
+        for name, x in planes.items():
+            check_tensor("compact", f"out[3][`{name}`]", dense[name], x.dtype, (capacity,) + words[name], align=16, device=self.device)
+        names = list(planes)
+        with torch.cuda.device(self.device):
+            for first in range(0, max(len(names), 1), _abi.COMPACT_MAX_PLANES):
+                part = names[first:first + _abi.COMPACT_MAX_PLANES]
+                io = _abi.PhxTrajCompactIO(T=T, n_planes=len(part), N=N, capacity=capacity, keep=_ptr(keep), start=_ptr(start),
+                                           out_row=_ptr(orow) if first == 0 else None, out_col=_ptr(ocol) if first == 0 else None)
+                for k, name in enumerate(part):
+                    io.plane[k] = _abi.PhxCompactPlane(src=_ptr(planes[name]), dst=_ptr(dense[name]),
+                                                       elem_bytes=planes[name].element_size() * int(np.prod(words[name])), reserved=0)
+                self._check(self.lib.phx_traj_compact(C.byref(io), self._stream()), "phx_traj_compact")
+        return start, orow, ocol, dense
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

@@ -420,7 +420,7 @@ class PhantomEnv:
         return traj
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
-               gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0)):
+               gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -465,7 +465,14 @@ class PhantomEnv:
         behaviour log-density is the rollout's ``action_logp``); plain envs only.  ``vf_next`` is built as above and one
         ``DeviceEnv.vtrace`` launch takes the place of the ``gae`` one, with ``vtrace_clip`` = RLlib's (clip_rho_threshold, the trace
         clip 1.0, clip_pg_rho_threshold): the batch carries ``vf_preds`` / ``target_logp`` / ``vtrace_vs`` / ``vtrace_pg_advantages``,
-        and ``advantages`` / ``value_targets`` stay None."""
+        and ``advantages`` / ``value_targets`` stay None.
+
+        ``compact=True`` (FSM / Stackelberg envs only; a plain env has no rows to drop: ValueError): the rows where no agent acted are
+        dropped ON THE DEVICE.  Everything above runs as it does without the keyword, on the time-major planes; then one
+        ``DeviceEnv.compact`` call with ``keep`` = who acted moves the kept elements of the columns ``to_sample_batches()`` would emit
+        into dense buffers in its row order, none of the transposes runs, and after the eight bytes of the kept count only the kept
+        rows are copied to the host.  The result is a ``phantom_amd.rollout.CompactFragment``: its ``to_sample_batches()`` equals the
+        ``FragmentBatch``'s; it has no step-aligned planes and no ``rollouts()``."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -483,6 +490,9 @@ class PhantomEnv:
                 raise ValueError("sample: `vtrace_clip` is (clip_rho_threshold, clip_c_threshold, clip_pg_rho_threshold)")
         dev = self._device()
         masked = self.spec.env_type != _abi.ENV_PLAIN            # per-agent trajectories with holes: validity planes, phx_gae_masked
+        if compact and not masked:
+            raise ValueError("sample: `compact` serves FSM / Stackelberg envs only (on a plain env every agent acts in every step: there "
+                             "is no row to drop)")
         kinds = self.spec.kind[self.spec.strategic_idx]
         if (self.spec.kind == _abi.KIND_ADVERTISER).any() or (masked and not np.isin(kinds, (_abi.KIND_SHOP, _abi.KIND_SELLER, _abi.KIND_BUYER)).all()):
             raise NotImplementedError("PhantomEnv.sample: envs whose strategic agents always return an observation when asked (shops, "
@@ -544,11 +554,14 @@ class PhantomEnv:
             piece_ends.append(done - 1)
         self._episodes_done = ep
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device
-        cols = {"obs": am(obs), "new_obs": am(new_obs), "actions": am(act), "rewards": am(rew), "terminateds": am(term),
-                "truncateds": am(trunc)}
+        if compact:
+            cols = {}                                            # (no transpose: the time-major planes go to DeviceEnv.compact below)
+        else:
+            cols = {"obs": am(obs), "new_obs": am(new_obs), "actions": am(act), "rewards": am(rew), "terminateds": am(term),
+                    "truncateds": am(trunc)}
         if explore:
             cols.update(raw_actions=am(raw), action_logp=am(logp), dist_inputs=am(dist))
-        if masked:
+        if masked and not compact:
             cols.update(obs_valid=am(acted), new_obs_valid=am(nvalid), reward_valid=am(rvalid))
 
         def values(x):                                                        # f32 [R, B, S, D] -> the critic's f32 [R, B, S]
@@ -577,8 +590,9 @@ class PhantomEnv:
         elif masked:
             # the agent's own view of the other three transition columns, over gae_masked's segments (before it: last_kernel() stays its)
             nrow, nterm, ntrunc, nobs = dev.traj_next(trunc, term, acted, nvalid, obs, new_obs)
-            cols.update(trajectory_next_row=am(nrow), trajectory_new_obs=am(nobs), trajectory_terminateds=am(nterm),
-                        trajectory_truncateds=am(ntrunc))
+            if not compact:
+                cols.update(trajectory_next_row=am(nrow), trajectory_new_obs=am(nobs), trajectory_terminateds=am(nterm),
+                            trajectory_truncateds=am(ntrunc))
             vf = vf_next = None
             if value_fn is not None:
                 with torch.no_grad():
@@ -594,6 +608,13 @@ class PhantomEnv:
                         vf_next[last] = values(held[None])[0]
                         first = last + 1
             adv, vt, rs = dev.gae_masked(rew, trunc, vf, vf_next, term, acted, rvalid, gamma, lambda_ if value_fn is not None else 1.0)
+            if compact:
+                planes = {"obs": obs, "new_obs": nobs, "actions": act, "rewards": rs, "terminateds": nterm, "truncateds": ntrunc,
+                          "trajectory_next_row": nrow}
+                if value_fn is not None:
+                    planes.update(vf_preds=vf, advantages=adv, value_targets=vt)
+                return self._compact_fragment(acted, planes, np.broadcast_to(t_in_ep, (B, T)).copy(),
+                                              (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64))
             cols.update(trajectory_rewards=am(rs))
             if value_fn is not None:
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
@@ -613,6 +634,40 @@ class PhantomEnv:
                              vtrace_vs=host.get("vtrace_vs"), vtrace_pg_advantages=host.get("vtrace_pg_advantages"),
                              trajectory_next_row=host.get("trajectory_next_row"), trajectory_new_obs=host.get("trajectory_new_obs"),
                              trajectory_terminateds=tbool("trajectory_terminateds"), trajectory_truncateds=tbool("trajectory_truncateds"))
+
+    def _compact_fragment(self, acted, planes, t, eps_id):
+        """sample(compact=True)'s exit: the kept elements of the time-major device ``planes`` ([T, B, S, ..], named as
+        ``to_sample_batches()``'s columns) as a CompactFragment.  One DeviceEnv.compact call into dense device buffers, the eight bytes
+        of the kept count K to the host, then rows [:K] of every buffer through pinned ones; both sets are kept per name and sized by
+        T * B * S once, as _to_pinned keeps its own"""
+        import torch
+        from .rollout import CompactFragment
+        dev = self._device()
+        T, B, S = acted.shape
+        N, cap = B * S, T * B * S
+        bufs = self.__dict__.setdefault("_compact_bufs", {})
+
+        def pair(name, shape, dtype):
+            have = bufs.get(name)
+            if have is None or tuple(have[0].shape) != shape or have[0].dtype != dtype:
+                have = bufs[name] = (torch.empty(shape, dtype=dtype, device=dev.device), torch.empty(shape, dtype=dtype, pin_memory=True))
+            return have
+        start_d, start_h = pair("col_start", (N + 1,), torch.int64)
+        row_d, row_h = pair("row", (cap,), torch.int32)
+        dense = {k: pair(k, (cap,) + tuple(x.shape[3:]), x.dtype) for k, x in planes.items()}
+        dev.compact(acted, planes, cap, out=(start_d, row_d, None, {k: d for k, (d, _) in dense.items()}))
+        K = int(start_d[N].item())                               # (the one wait before the copies: how many rows leave the device)
+        start_h.copy_(start_d, non_blocking=True)
+        row_h[:K].copy_(row_d[:K], non_blocking=True)
+        for d, h in dense.values():
+            h[:K].copy_(d[:K], non_blocking=True)
+        torch.cuda.current_stream(dev.device).synchronize()
+        cols = {k: h[:K].numpy() for k, (_, h) in dense.items()}
+        for k in ("terminateds", "truncateds"):
+            cols[k] = cols[k].view(np.bool_)                     # (the kernels write 0 / 1)
+        cols["actions"] = cols["actions"].reshape(K, 1)
+        ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
+        return CompactFragment(ids, B, S, T, start_h.numpy(), row_h[:K].numpy(), t, eps_id, cols)
 
     def _noise_generator(self, device):
         """the env's own generator of exploration noise on ``device``, seeded from (seed, env_offset): shards draw independently"""

@@ -316,6 +316,89 @@ class FragmentBatch:
         return out
 
 
+class CompactFragment:
+    """The rows of an FSM / Stackelberg fragment where an agent acted, and nothing else: what ``PhantomEnv.sample(compact=True)``
+    returns.  The hole rows were dropped on the device (``DeviceEnv.compact``, include/phantom_amd_compact.h), so every array here is
+    already in ``to_sample_batches()``'s row order -- (env instance, agent, step) -- and K rows long.
+
+    ``agent_ids``; ``B``, ``S``, ``T`` as in ``FragmentBatch``; ``K`` the number of kept rows
+    ``col_start`` i64 [B * S + 1]: the rows of (env instance b, agent s) are ``[col_start[b * S + s], col_start[b * S + s + 1])``
+    ``row``       i32 [K] the fragment row (step) of every kept row
+    ``t``         i32 [B, T], ``eps_id`` i64 [B, T] as in ``FragmentBatch``
+    ``columns``   {name: [K, ..] host array} under ``to_sample_batches()``'s column names: ``obs``, ``new_obs`` (the agent's NEXT
+                  observation), ``actions``, ``rewards`` (the transition's), ``terminateds`` / ``truncateds`` (bool, the transition's),
+                  ``trajectory_next_row`` (a FRAGMENT row, as in ``FragmentBatch``), with a critic ``vf_preds`` / ``advantages`` /
+                  ``value_targets``
+
+    The arrays of a fragment that ``sample(compact=True)`` returned are views of host buffers the env keeps: they hold until the
+    env's next ``sample(compact=True)`` call.  There is no ``rollouts()`` / ``step()`` here -- the step-aligned planes never left the
+    device: use ``compact=False`` for the reference's containers."""
+
+    ORDER = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
+
+    def __init__(self, agent_ids, B: int, S: int, T: int, col_start, row, t, eps_id, columns):
+        self.agent_ids = list(agent_ids)
+        self.B, self.S, self.T = int(B), int(S), int(T)
+        self.col_start, self.row, self.t, self.eps_id = col_start, row, t, eps_id
+        self.K = int(col_start[-1])
+        self.columns = dict(columns)
+        if len(self.agent_ids) != self.S or col_start.shape != (self.B * self.S + 1,) or row.shape != (self.K,):
+            raise ValueError("CompactFragment: col_start is [B * S + 1], row is [K = col_start[-1]] and there is one agent id per S")
+        for k, v in self.columns.items():
+            if v.shape[0] != self.K:
+                raise ValueError(f"CompactFragment: column `{k}` has {v.shape[0]} rows, expected K = {self.K}")
+
+    @classmethod
+    def from_time_major(cls, agent_ids, keep, columns, t, eps_id, action_shape=(1,)):
+        """from TIME-major host arrays, by the numpy restatement of the compaction: ``keep`` u8 / bool [T, B, S], every column
+        [T, B, S, ..] under its ``to_sample_batches()`` name (``terminateds`` / ``truncateds`` become bool, ``actions`` take
+        ``action_shape``), ``t`` / ``eps_id`` [B, T]"""
+        keep = np.asarray(keep)
+        T, B, S = keep.shape
+        km = np.moveaxis(keep, 0, 2) != 0                                 # [B, S, T]
+        col_start = np.zeros(B * S + 1, dtype=np.int64)
+        np.cumsum(km.reshape(B * S, T).sum(axis=1), out=col_start[1:])
+        row = np.broadcast_to(np.arange(T, dtype=np.int32), (B, S, T))[km]
+        cols = {}
+        for k, v in columns.items():
+            c = np.moveaxis(np.asarray(v), 0, 2)[km]
+            if k in ("terminateds", "truncateds"):
+                c = c.astype(bool)
+            elif k == "actions":
+                c = c.reshape((len(c),) + tuple(action_shape))
+            elif k in ("obs", "new_obs"):
+                c = c.reshape(len(c), int(np.prod(c.shape[1:])))
+            cols[k] = c
+        return cls(agent_ids, B, S, T, col_start, row, t, eps_id, cols)
+
+    def to_sample_batches(self, policy_mapping_fn: Optional[Callable[[Any], str]] = None) -> Dict[str, Dict[str, np.ndarray]]:
+        """what ``FragmentBatch.to_sample_batches`` returns for the same fragment, key for key and array for array.  With every agent
+        under one policy the columns are ``self.columns``' arrays themselves (no copy); a policy that owns a subset of the agents
+        takes its agents' ranges from ``col_start`` (one indexed copy per column).  ``eps_id``, ``t``, ``env_id`` and ``agent_index``
+        are derived here from ``row`` and ``col_start``."""
+        fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
+        groups: Dict[str, List[int]] = {}
+        for s, aid in enumerate(self.agent_ids):
+            groups.setdefault(fn(aid), []).append(s)
+        B, S = self.B, self.S
+        counts = np.diff(self.col_start)
+        col = np.repeat(np.arange(B * S, dtype=np.int32), counts)         # the column of every kept row
+        env_id, agent_index = col // S, col % S
+        derived = {"eps_id": self.eps_id[env_id, self.row], "agent_index": agent_index, "t": self.t[env_id, self.row], "env_id": env_id}
+        names = list(self.ORDER) + list(derived) + [k for k in self.columns if k not in self.ORDER]
+        out = {}
+        for pid, idx in groups.items():
+            if idx == list(range(S)):
+                sel = lambda a: a
+            else:
+                cols_of = (np.arange(B)[:, None] * S + np.asarray(idx)[None, :]).reshape(-1)
+                first, n = self.col_start[cols_of], counts[cols_of]
+                rows = np.repeat(first - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))
+                sel = lambda a: a[rows]
+            out[pid] = {k: sel(self.columns[k] if k in self.columns else derived[k]) for k in names if k in self.columns or k in derived}
+        return out
+
+
 def fragment_from_arrays(agent_ids, first_obs, new_obs, actions, rewards, terminated, truncated, num_steps: int, step0,
                          reset_obs: Optional[Dict[int, np.ndarray]] = None, obs_valid=None, reward_valid=None,
                          first_obs_valid=None, stage=None, stage_ids=None, episode0: int = 0,
