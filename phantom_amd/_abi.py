@@ -172,6 +172,13 @@ class PhxTrajCompactIO(C.Structure):
                 ("start", C.c_void_p), ("out_row", C.c_void_p), ("out_col", C.c_void_p), ("plane", PhxCompactPlane * COMPACT_MAX_PLANES)]
 
 
+class PhxNstepIO(C.Structure):
+    """phx_nstep_io (include/phantom_amd_nstep.h): the planes of one phx_nstep call"""
+    _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("N", C.c_int64), ("n", C.c_int32), ("gamma", C.c_float)] + [
+        (n, C.c_void_p) for n in ("reward", "truncated", "terminated", "acted", "next_row", "next_obs", "succ_row", "nstep_reward",
+                                  "nstep_discount", "nstep_last", "nstep_terminated", "nstep_truncated", "nstep_next_row", "nstep_next_obs")]
+
+
 GAE_KERNEL = "phx_gae_kernel"
 GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
 VTRACE_KERNEL = "phx_vtrace_kernel"
@@ -181,6 +188,10 @@ COMPACT_COUNT_KERNEL = "phx_compact_count_kernel"        # (phx_traj_compact: th
 COMPACT_SCAN_KERNEL = "phx_compact_scan_kernel"          #  where it has nothing to write)
 COMPACT_SCATTER_KERNEL = "phx_compact_scatter_kernel"
 COMPACT_KERNELS = "+".join((COMPACT_COUNT_KERNEL, COMPACT_SCAN_KERNEL, COMPACT_SCATTER_KERNEL))
+NSTEP_SUCC_KERNEL = "phx_nstep_succ_kernel"              # (phx_nstep: the names of the kernels launched joined by "+"; the scan's only with
+NSTEP_FOLD_KERNEL = "phx_nstep_fold_kernel"              #  `acted`, the gather's only with nstep_next_obs)
+NSTEP_GATHER_KERNEL = "phx_nstep_gather_kernel"
+NSTEP_MAX_N = 64
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -189,6 +200,8 @@ assert C.sizeof(PhxMsgRec) == 16
 assert C.sizeof(PhxVtraceIO) == 112      # (stated in include/phantom_amd_vtrace.h)
 assert C.sizeof(PhxTrajNextIO) == 96     # (stated in include/phantom_amd_traj.h)
 assert C.sizeof(PhxCompactPlane) == 24 and C.sizeof(PhxTrajCompactIO) == 440      # (stated in include/phantom_amd_compact.h)
+assert C.sizeof(PhxNstepIO) == 136 and PhxNstepIO.reward.offset == 24 and PhxNstepIO.succ_row.offset == 72      # (stated in include/phantom_amd_nstep.h)
+assert PhxNstepIO.n.offset == 16 and PhxNstepIO.gamma.offset == 20 and PhxNstepIO.nstep_next_obs.offset == 128
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -309,6 +322,13 @@ def bind_compact(lib):
     return lib
 
 
+def bind_nstep(lib):
+    """restype / argtypes of include/phantom_amd_nstep.h's entry point: libphantom_amd.so only, like bind_compact"""
+    lib.phx_nstep.restype = C.c_int32
+    lib.phx_nstep.argtypes = [C.POINTER(PhxNstepIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -328,6 +348,7 @@ def load_library():
     bind_vtrace(lib)
     bind_traj(lib)
     bind_compact(lib)
+    bind_nstep(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -832,6 +832,76 @@ class DeviceEnv:
             self._check(self.lib.phx_traj_next(C.byref(io), self._stream()), "phx_traj_next")
         return nr, nte, ntr, nob
 
+    def nstep(self, rewards, truncations, terminations=None, acted=None, next_row=None, next_obs=None, n: int = 3, gamma: float = 0.99,
+              out=None):
+        """``(nstep_rewards, nstep_discounts, nstep_last, nstep_terminateds, nstep_truncateds, nstep_next_row, nstep_next_obs or None)``:
+        the n-step transitions of a time-major fragment for a replay learner (RLlib's ``adjust_nstep``, over trajectories with holes as
+        well), on the current stream (phx_nstep, include/phantom_amd_nstep.h).  The inputs describe one TRANSITION per trajectory row:
+        on an FSM / Stackelberg env ``rewards`` is ``gae_masked``'s ``trajectory_rewards`` and ``truncations`` / ``terminations`` /
+        ``next_row`` / ``next_obs`` are ``traj_next``'s four results, with the same ``acted``; on a plain env they are the rollout's own
+        ``rewards`` / ``truncations`` / ``terminations`` / ``observations`` planes and ``acted`` and ``next_row`` stay None.  Planes are
+        ``[T, B, S]`` (or ``[T, N]``) on the env's device -- ``rewards`` f32, the flags and ``acted`` u8, ``next_row`` i32 -- and
+        ``next_obs`` f32 ``[T, B, S, D]``, D <= 64; slices of longer recordings are fine.  At a row where the agent acted the call folds
+        the rewards of up to ``n`` of the agent's consecutive transitions, ``r0 + gamma r1 + ..`` (f32 ``fmaf`` chain), stopping after a
+        transition with a done flag, at the agent's last trajectory row, and before a transition that is incomplete (``next_row`` -1
+        without a flag; an incomplete row itself folds only its own reward); ``nstep_discounts`` is gamma to the number of transitions
+        folded, ``nstep_last`` (i32) the row of the last one, the two u8 flags and ``nstep_next_row`` (i32) are that row's, and
+        ``nstep_next_obs`` (only with ``next_obs``; a further launch) its ``next_obs`` bit for bit: the learner's target is
+        ``nstep_rewards + nstep_discounts * (1 - nstep_terminateds) * Q(nstep_next_obs)``.  Rows that are no trajectory rows hold +0.0,
+        +0.0, -1, 0, 0, -1 and +0.0.  ``n`` in [1, 64] (1: the inputs themselves), ``gamma`` in [0, 1].  ``out``: the seven result
+        tensors (the last one None without ``next_obs``), 16-byte aligned, optionally followed by an eighth, the i32 ``[T, B, S]`` scratch
+        that receives every row's next trajectory row (``succ_row``, used with ``acted`` only); whatever is missing is allocated here
+        with ``torch.empty`` -- the caching allocator's stream-ordered reuse makes a per-call scratch safe, and a caller that captures the
+        call into a graph or wants no allocation passes all eight.  The call does not synchronise."""
+        torch = _torch()
+        f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+        if rewards is None or not hasattr(rewards, "dim") or rewards.dim() < 2:
+            raise ValueError("nstep: `rewards` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(rewards.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"nstep: `rewards` has shape {shape}: T and N must be >= 1")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= _abi.NSTEP_MAX_N:
+            raise ValueError(f"nstep: n = {n!r} must be an int in [1, {_abi.NSTEP_MAX_N}]")
+        if not 0.0 <= float(np.float32(gamma)) <= 1.0:           # (as the struct holds it; NaN fails both comparisons)
+            raise ValueError(f"nstep: gamma = {gamma} must lie in [0, 1]")
+        check_tensor("nstep", "rewards", rewards, f32, shape, device=self.device)
+        check_tensor("nstep", "truncations", truncations, u8, shape, device=self.device)
+        for name, x, dtype in (("terminations", terminations, u8), ("acted", acted, u8), ("next_row", next_row, i32)):
+            if x is not None:
+                check_tensor("nstep", name, x, dtype, shape, device=self.device)
+        gather, D = next_obs is not None, 0
+        if gather:
+            if not hasattr(next_obs, "dim") or next_obs.dim() != len(shape) + 1 or not 1 <= next_obs.shape[-1] <= 64:
+                raise ValueError(f"nstep: `next_obs` must be a {shape + ('D',)} tensor with 1 <= D <= 64")
+            D = int(next_obs.shape[-1])
+            check_tensor("nstep", "next_obs", next_obs, f32, shape + (D,), device=self.device)
+        e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+        if out is None:
+            out = (e(shape, f32), e(shape, f32), e(shape, i32), e(shape, u8), e(shape, u8), e(shape, i32), e(shape + (D,), f32) if gather else None)
+        if len(out) not in (7, 8):
+            raise ValueError("nstep: `out` is (nstep_rewards, nstep_discounts, nstep_last, nstep_terminateds, nstep_truncateds, "
+                             "nstep_next_row, nstep_next_obs or None[, succ_row])")
+        res, succ = tuple(out[:7]), (out[7] if len(out) == 8 else None)
+        for i, (x, dtype) in enumerate(zip(res[:6], (f32, f32, i32, u8, u8, i32))):
+            check_tensor("nstep", f"out[{i}]", x, dtype, shape, align=16, device=self.device)
+        if gather:
+            check_tensor("nstep", "out[6]", res[6], f32, shape + (D,), align=16, device=self.device)
+        elif res[6] is not None:
+            raise ValueError("nstep: `out[6]` (nstep_next_obs) needs `next_obs`")
+        if succ is not None:
+            check_tensor("nstep", "out[7]", succ, i32, shape, align=16, device=self.device)
+        elif acted is not None:
+            succ = e(shape, i32)
+        io = _abi.PhxNstepIO(T=T, D=D, N=N, n=int(n), gamma=gamma, reward=_ptr(rewards), truncated=_ptr(truncations),
+                             terminated=_ptr(terminations), acted=_ptr(acted), next_row=_ptr(next_row), next_obs=_ptr(next_obs),
+                             succ_row=_ptr(succ), nstep_reward=_ptr(res[0]), nstep_discount=_ptr(res[1]), nstep_last=_ptr(res[2]),
+                             nstep_terminated=_ptr(res[3]), nstep_truncated=_ptr(res[4]), nstep_next_row=_ptr(res[5]),
+                             nstep_next_obs=_ptr(res[6]))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_nstep(C.byref(io), self._stream()), "phx_nstep")
+        return res
+
     def compact(self, keep, planes, capacity=None, out=None):
         """``(start, out_row, out_col, {name: dense tensor})``: the kept elements of time-major planes, dense and in (column, row) =
         (env instance, agent, step) order, on the current stream (phx_traj_compact, include/phantom_amd_compact.h) -- the hole rows of

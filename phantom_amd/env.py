@@ -420,7 +420,8 @@ class PhantomEnv:
         return traj
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
-               gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False):
+               gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False,
+               n_step=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -472,11 +473,27 @@ class PhantomEnv:
         ``DeviceEnv.compact`` call with ``keep`` = who acted moves the kept elements of the columns ``to_sample_batches()`` would emit
         into dense buffers in its row order, none of the transposes runs, and after the eight bytes of the kept count only the kept
         rows are copied to the host.  The result is a ``phantom_amd.rollout.CompactFragment``: its ``to_sample_batches()`` equals the
-        ``FragmentBatch``'s; it has no step-aligned planes and no ``rollouts()``."""
+        ``FragmentBatch``'s; it has no step-aligned planes and no ``rollouts()``.
+
+        ``n_step``: a replay learner's batch (DQN / SAC / TD3 / DDPG with ``n_step > 1``; RLlib's ``adjust_nstep``).  None: nothing of
+        this runs.  An int in [1, 64]: after everything above one ``DeviceEnv.nstep`` call folds, at every row where an agent acted, the
+        rewards of up to ``n_step`` of the agent's own consecutive transitions with ``gamma``, and the batch carries ``nstep_rewards``,
+        ``nstep_discounts`` (gamma to the number of transitions folded), ``nstep_new_obs``, ``nstep_terminateds`` and ``nstep_truncateds``
+        (of the last transition folded): the target is ``nstep_rewards + nstep_discounts * (1 - nstep_terminateds) * Q(nstep_new_obs)``.
+        On a plain env, with or without ``policy`` / ``value_fn``, the transitions are the step-aligned ``rewards`` / ``terminateds`` /
+        ``truncateds`` / ``new_obs``; on an FSM / Stackelberg env they are ``trajectory_rewards`` and the four ``trajectory_`` fields, a chain
+        runs over the rows where the agent acted and never folds an incomplete transition into an earlier row.  A chain stops at a done
+        flag and at the fragment's end.  The one-step fields and columns stay as they are; with ``compact=True`` the five columns are
+        compacted with the rest."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
             raise ValueError("sample: `policy` and replayed `actions` exclude each other")
+        if n_step is not None:
+            if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= _abi.NSTEP_MAX_N:
+                raise ValueError(f"sample: n_step = {n_step!r} must be None or an int in [1, {_abi.NSTEP_MAX_N}]")
+            if not 0.0 <= float(np.float32(gamma)) <= 1.0:
+                raise ValueError(f"sample: n_step folds rewards with gamma = {gamma}, which must lie in [0, 1]")
         if explore and (policy is None or not policy.stochastic):
             raise ValueError("sample: explore=True needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
         if target_logp_fn is not None:
@@ -587,7 +604,11 @@ class PhantomEnv:
             else:
                 adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
-        elif masked:
+        if n_step is not None and not masked:                    # the step-aligned planes are the transitions: every row complete
+            ns = dev.nstep(rew, trunc, term, None, None, new_obs, int(n_step), gamma)
+            cols.update(nstep_rewards=am(ns[0]), nstep_discounts=am(ns[1]), nstep_new_obs=am(ns[6]), nstep_terminateds=am(ns[3]),
+                        nstep_truncateds=am(ns[4]))
+        if masked:
             # the agent's own view of the other three transition columns, over gae_masked's segments (before it: last_kernel() stays its)
             nrow, nterm, ntrunc, nobs = dev.traj_next(trunc, term, acted, nvalid, obs, new_obs)
             if not compact:
@@ -608,14 +629,22 @@ class PhantomEnv:
                         vf_next[last] = values(held[None])[0]
                         first = last + 1
             adv, vt, rs = dev.gae_masked(rew, trunc, vf, vf_next, term, acted, rvalid, gamma, lambda_ if value_fn is not None else 1.0)
+            ns = None
+            if n_step is not None:                               # the agent's own transitions: gae_masked's rewards, traj_next's other columns
+                ns = dev.nstep(rs, ntrunc, nterm, acted, nrow, nobs, int(n_step), gamma)
+                ns = dict(nstep_rewards=ns[0], nstep_discounts=ns[1], nstep_new_obs=ns[6], nstep_terminateds=ns[3], nstep_truncateds=ns[4])
             if compact:
                 planes = {"obs": obs, "new_obs": nobs, "actions": act, "rewards": rs, "terminateds": nterm, "truncateds": ntrunc,
                           "trajectory_next_row": nrow}
                 if value_fn is not None:
                     planes.update(vf_preds=vf, advantages=adv, value_targets=vt)
+                if ns is not None:
+                    planes.update(ns)
                 return self._compact_fragment(acted, planes, np.broadcast_to(t_in_ep, (B, T)).copy(),
                                               (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64))
             cols.update(trajectory_rewards=am(rs))
+            if ns is not None:
+                cols.update({k: am(x) for k, x in ns.items()})
             if value_fn is not None:
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         host = self._to_pinned(cols)
@@ -633,7 +662,10 @@ class PhantomEnv:
                              trajectory_rewards=host.get("trajectory_rewards"), target_logp=host.get("target_logp"),
                              vtrace_vs=host.get("vtrace_vs"), vtrace_pg_advantages=host.get("vtrace_pg_advantages"),
                              trajectory_next_row=host.get("trajectory_next_row"), trajectory_new_obs=host.get("trajectory_new_obs"),
-                             trajectory_terminateds=tbool("trajectory_terminateds"), trajectory_truncateds=tbool("trajectory_truncateds"))
+                             trajectory_terminateds=tbool("trajectory_terminateds"), trajectory_truncateds=tbool("trajectory_truncateds"),
+                             nstep_rewards=host.get("nstep_rewards"), nstep_discounts=host.get("nstep_discounts"),
+                             nstep_new_obs=host.get("nstep_new_obs"), nstep_terminateds=tbool("nstep_terminateds"),
+                             nstep_truncateds=tbool("nstep_truncateds"))
 
     def _compact_fragment(self, acted, planes, t, eps_id):
         """sample(compact=True)'s exit: the kept elements of the time-major device ``planes`` ([T, B, S, ..], named as
@@ -663,8 +695,9 @@ class PhantomEnv:
             h[:K].copy_(d[:K], non_blocking=True)
         torch.cuda.current_stream(dev.device).synchronize()
         cols = {k: h[:K].numpy() for k, (_, h) in dense.items()}
-        for k in ("terminateds", "truncateds"):
-            cols[k] = cols[k].view(np.bool_)                     # (the kernels write 0 / 1)
+        for k in ("terminateds", "truncateds", "nstep_terminateds", "nstep_truncateds"):
+            if k in cols:
+                cols[k] = cols[k].view(np.bool_)                 # (the kernels write 0 / 1)
         cols["actions"] = cols["actions"].reshape(K, 1)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         return CompactFragment(ids, B, S, T, start_h.numpy(), row_h[:K].numpy(), t, eps_id, cols)

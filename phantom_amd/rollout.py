@@ -152,6 +152,9 @@ class Rollout:
         return f"Rollout(rollout_id={self.rollout_id}, repeat_id={self.repeat_id}, steps={len(self.steps)})"
 
 
+NSTEP_COLUMNS = ("nstep_rewards", "nstep_discounts", "nstep_new_obs", "nstep_terminateds", "nstep_truncateds")
+
+
 class FragmentBatch:
     """A rollout fragment on the host, agent-major: every array is ``[B, S, T, ..]`` (env instance, strategic agent, step).
 
@@ -178,6 +181,11 @@ class FragmentBatch:
     an off-policy learner's fragment (PhantomEnv.sample(target_logp_fn=...)), else None -- ``advantages`` / ``value_targets`` are None then:
     ``target_logp`` f32 [B, S, T] the learner's log-density of the recorded draws
     ``vtrace_vs`` / ``vtrace_pg_advantages`` f32 [B, S, T] V-trace value targets and policy-gradient advantages (DeviceEnv.vtrace)
+    a replay learner's fragment (PhantomEnv.sample(n_step=n)), else None -- DeviceEnv.nstep over the agent's own transitions:
+    ``nstep_rewards`` f32 [B, S, T] the discounted sum of the rewards of the (up to n) transitions folded at the row
+    ``nstep_discounts`` f32 [B, S, T] gamma to the number of transitions folded: what to multiply Q(``nstep_new_obs``) with
+    ``nstep_new_obs`` f32 [B, S, T, D], ``nstep_terminateds`` / ``nstep_truncateds`` bool [B, S, T] the next observation and the done
+    flags of the last transition folded; +0.0 / False at rows where the agent did not act.  The one-step fields stay as they are
     """
 
     COLUMNS = ("obs", "new_obs", "actions", "rewards", "terminateds", "truncateds")
@@ -187,7 +195,8 @@ class FragmentBatch:
                  action_shape=(1,), never_finishes_alone: bool = True, done_valid=None, raw_actions=None, action_logp=None,
                  dist_inputs=None, vf_preds=None, advantages=None, value_targets=None, trajectory_rewards=None, target_logp=None,
                  vtrace_vs=None, vtrace_pg_advantages=None, trajectory_next_row=None, trajectory_new_obs=None,
-                 trajectory_terminateds=None, trajectory_truncateds=None):
+                 trajectory_terminateds=None, trajectory_truncateds=None, nstep_rewards=None, nstep_discounts=None, nstep_new_obs=None,
+                 nstep_terminateds=None, nstep_truncateds=None):
         self.agent_ids = list(agent_ids)
         self.obs, self.new_obs, self.actions, self.rewards = obs, new_obs, actions, rewards
         self.terminateds, self.truncateds, self.t, self.eps_id = terminateds, truncateds, t, eps_id
@@ -202,6 +211,8 @@ class FragmentBatch:
         self.trajectory_next_row, self.trajectory_new_obs = trajectory_next_row, trajectory_new_obs
         self.trajectory_terminateds, self.trajectory_truncateds = trajectory_terminateds, trajectory_truncateds
         self.target_logp, self.vtrace_vs, self.vtrace_pg_advantages = target_logp, vtrace_vs, vtrace_pg_advantages
+        self.nstep_rewards, self.nstep_discounts, self.nstep_new_obs = nstep_rewards, nstep_discounts, nstep_new_obs
+        self.nstep_terminateds, self.nstep_truncateds = nstep_terminateds, nstep_truncateds
         self.B, self.S, self.T = obs.shape[0], obs.shape[1], obs.shape[2]
 
     # ---- RLlib-shaped exit -------------------------------------------------------------------------------------------
@@ -218,7 +229,8 @@ class FragmentBatch:
         ``trajectory_new_obs`` / ``trajectory_terminateds`` / ``trajectory_truncateds`` its ``new_obs`` / ``terminateds`` / ``truncateds``
         columns from those (the agent's next observation and the flags of the step that ended its transition), plus a
         ``trajectory_next_row`` column: a row is a complete transition iff it carries a flag or ``trajectory_next_row >= 0`` (only an
-        agent's last row of the fragment can be incomplete)."""
+        agent's last row of the fragment can be incomplete).  A fragment with ``nstep_rewards`` / ``nstep_discounts`` / ``nstep_new_obs`` /
+        ``nstep_terminateds`` / ``nstep_truncateds`` has the columns of those names next to the one-step ones."""
         fn = policy_mapping_fn or (lambda aid: DEFAULT_POLICY_ID)
         groups: Dict[str, List[int]] = {}
         for s, aid in enumerate(self.agent_ids):
@@ -259,6 +271,10 @@ class FragmentBatch:
             for name in ("vf_preds", "advantages", "value_targets", "target_logp", "vtrace_vs", "vtrace_pg_advantages"):
                 if getattr(self, name) is not None:
                     cols[name] = sel(getattr(self, name)).reshape(-1)
+            for name in NSTEP_COLUMNS:
+                if getattr(self, name) is not None:
+                    x = sel(getattr(self, name))
+                    cols[name] = x.reshape(B * n * T, -1) if name == "nstep_new_obs" else x.reshape(-1)
             if self.obs_valid is not None:
                 keep = sel(self.obs_valid).reshape(-1).astype(bool)
                 cols = {k: v[keep] for k, v in cols.items()}
@@ -328,7 +344,8 @@ class CompactFragment:
     ``columns``   {name: [K, ..] host array} under ``to_sample_batches()``'s column names: ``obs``, ``new_obs`` (the agent's NEXT
                   observation), ``actions``, ``rewards`` (the transition's), ``terminateds`` / ``truncateds`` (bool, the transition's),
                   ``trajectory_next_row`` (a FRAGMENT row, as in ``FragmentBatch``), with a critic ``vf_preds`` / ``advantages`` /
-                  ``value_targets``
+                  ``value_targets``, with ``n_step`` ``nstep_rewards`` / ``nstep_discounts`` / ``nstep_new_obs`` / ``nstep_terminateds`` /
+                  ``nstep_truncateds`` (the flags bool)
 
     The arrays of a fragment that ``sample(compact=True)`` returned are views of host buffers the env keeps: they hold until the
     env's next ``sample(compact=True)`` call.  There is no ``rollouts()`` / ``step()`` here -- the step-aligned planes never left the
