@@ -179,6 +179,25 @@ class PhxNstepIO(C.Structure):
                                   "nstep_discount", "nstep_last", "nstep_terminated", "nstep_truncated", "nstep_next_row", "nstep_next_obs")]
 
 
+class PhxEpisodeStats(C.Structure):
+    """struct phx_episode_stats (include/phantom_amd_episodes.h): one element of col_stats / summary"""
+    _fields_ = [("count", C.c_int64), ("len_sum", C.c_int64), ("ret_sum", C.c_double), ("ret_sumsq", C.c_double),
+                ("ret_min", C.c_float), ("ret_max", C.c_float), ("len_min", C.c_int32), ("len_max", C.c_int32)]
+
+
+class PhxEpisodeIO(C.Structure):
+    """phx_episode_io (include/phantom_amd_episodes.h): the planes of one phx_episode_stats call"""
+    _fields_ = [("T", C.c_int32), ("G", C.c_int32), ("N", C.c_int64), ("K", C.c_int32), ("reserved0", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("reward", "truncated", "terminated", "acted", "reward_valid", "carry_return", "carry_len",
+                                  "episode_return", "episode_len", "col_stats", "summary")]
+
+
+# the same 48 bytes as a numpy record: np.frombuffer / ndarray.view of a uint8 [.., 48] host copy of col_stats / summary
+EPISODE_STATS_DTYPE = [("count", "<i8"), ("len_sum", "<i8"), ("ret_sum", "<f8"), ("ret_sumsq", "<f8"), ("ret_min", "<f4"),
+                       ("ret_max", "<f4"), ("len_min", "<i4"), ("len_max", "<i4")]
+EPISODE_STATS_BYTES = 48
+EPISODE_MAX_G = 256
+
 GAE_KERNEL = "phx_gae_kernel"
 GAE_MASKED_KERNEL = "phx_gae_masked_kernel"
 VTRACE_KERNEL = "phx_vtrace_kernel"
@@ -192,6 +211,8 @@ NSTEP_SUCC_KERNEL = "phx_nstep_succ_kernel"              # (phx_nstep: the names
 NSTEP_FOLD_KERNEL = "phx_nstep_fold_kernel"              #  `acted`, the gather's only with nstep_next_obs)
 NSTEP_GATHER_KERNEL = "phx_nstep_gather_kernel"
 NSTEP_MAX_N = 64
+EPISODE_SCAN_KERNEL = "phx_episode_scan_kernel"          # (phx_episode_stats: the scan's name, with `summary` joined by "+" with the
+EPISODE_REDUCE_KERNEL = "phx_episode_reduce_kernel"      #  reduction's)
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -202,6 +223,10 @@ assert C.sizeof(PhxTrajNextIO) == 96     # (stated in include/phantom_amd_traj.h
 assert C.sizeof(PhxCompactPlane) == 24 and C.sizeof(PhxTrajCompactIO) == 440      # (stated in include/phantom_amd_compact.h)
 assert C.sizeof(PhxNstepIO) == 136 and PhxNstepIO.reward.offset == 24 and PhxNstepIO.succ_row.offset == 72      # (stated in include/phantom_amd_nstep.h)
 assert PhxNstepIO.n.offset == 16 and PhxNstepIO.gamma.offset == 20 and PhxNstepIO.nstep_next_obs.offset == 128
+assert C.sizeof(PhxEpisodeStats) == EPISODE_STATS_BYTES == 48      # (stated in include/phantom_amd_episodes.h, as is every offset below)
+assert [getattr(PhxEpisodeStats, n).offset for n, _ in PhxEpisodeStats._fields_] == [0, 8, 16, 24, 32, 36, 40, 44]
+assert C.sizeof(PhxEpisodeIO) == 112
+assert [getattr(PhxEpisodeIO, n).offset for n, _ in PhxEpisodeIO._fields_] == [0, 4, 8, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96, 104]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -329,6 +354,13 @@ def bind_nstep(lib):
     return lib
 
 
+def bind_episode(lib):
+    """restype / argtypes of include/phantom_amd_episodes.h's entry point: libphantom_amd.so only, like bind_nstep"""
+    lib.phx_episode_stats.restype = C.c_int32
+    lib.phx_episode_stats.argtypes = [C.POINTER(PhxEpisodeIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -349,6 +381,7 @@ def load_library():
     bind_traj(lib)
     bind_compact(lib)
     bind_nstep(lib)
+    bind_episode(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -902,6 +902,75 @@ class DeviceEnv:
             self._check(self.lib.phx_nstep(C.byref(io), self._stream()), "phx_nstep")
         return res
 
+    def episode_stats(self, rewards, truncations, terminations=None, acted=None, reward_valid=None, group: int = 1, classes: int = 1,
+                      carry=None, planes: bool = False, summary: bool = True, out=None):
+        """``(col_stats, summary or None, episode_return or None, episode_len or None)``: the returns and lengths of the episodes that
+        close inside a time-major fragment, on the current stream (phx_episode_stats, include/phantom_amd_episodes.h).  Planes are
+        ``[T, B, S]`` (or ``[T, N]``) on the env's device -- ``rewards`` f32, the flags, ``acted`` and ``reward_valid`` u8, as a rollout
+        wrote them; slices of longer recordings are fine; a missing ``terminations`` reads as all zero, a missing ``acted`` or
+        ``reward_valid`` as all one (a plain env).  ``group`` consecutive input columns form an output column (1: one per (env
+        instance, agent); S: one per env instance, RLlib's episode -- it closes in the row where every member carries a flag), C =
+        N / group of them, and output column c belongs to class c % ``classes``.  ``carry`` is a ``(f32 [C], i32 [C])`` pair of device
+        tensors holding each output column's open episode (return so far, length so far; -1: none open), read and updated in place:
+        an episode a fragment cuts is finished by the next call.  None: every column starts with no episode open and what is open at
+        the end is dropped.  ``col_stats`` is uint8 ``[C, 48]`` and ``summary`` (``summary=True``; a second launch) uint8
+        ``[classes, 48]``: records of ``_abi.EPISODE_STATS_DTYPE`` (count, len_sum, ret_sum, ret_sumsq, ret_min, ret_max, len_min,
+        len_max) of the episodes THIS call closed, per output column and per class; a host copy is viewed with
+        ``.numpy().view(_abi.EPISODE_STATS_DTYPE)``.  With ``planes=True`` ``episode_return`` (f32) and ``episode_len`` (i32), both
+        ``[T, C]``, hold the return and length at the rows that close an episode and +0.0 / -1 elsewhere.  ``out``: the same four,
+        caller-owned and 16-byte aligned (None where a result is not wanted: ``planes`` and ``summary`` are then read from it);
+        allocated here when None.  The call does not synchronise."""
+        torch = _torch()
+        f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+        if rewards is None or not hasattr(rewards, "dim") or rewards.dim() < 2:
+            raise ValueError("episode_stats: `rewards` must be a [T, B, S] (or [T, N]) tensor")
+        shape = tuple(rewards.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"episode_stats: `rewards` has shape {shape}: T and N must be >= 1")
+        for name, v, hi in (("group", group, _abi.EPISODE_MAX_G), ("classes", classes, None)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or (hi is not None and v > hi):
+                raise ValueError(f"episode_stats: {name} = {v!r} must be an int >= 1" + (f" and <= {hi}" if hi else ""))
+        if N % group:
+            raise ValueError(f"episode_stats: group = {group} must divide the {N} input columns")
+        Cn = N // int(group)
+        if Cn % classes or classes >= 2 ** 31:
+            raise ValueError(f"episode_stats: classes = {classes} must divide the {Cn} output columns")
+        check_tensor("episode_stats", "rewards", rewards, f32, shape, device=self.device)
+        check_tensor("episode_stats", "truncations", truncations, u8, shape, device=self.device)
+        for name, x in (("terminations", terminations), ("acted", acted), ("reward_valid", reward_valid)):
+            if x is not None:
+                check_tensor("episode_stats", name, x, u8, shape, device=self.device)
+        cr = cl = None
+        if carry is not None:
+            if len(carry) != 2:
+                raise ValueError("episode_stats: `carry` is a (f32 [C], i32 [C]) pair of device tensors")
+            cr, cl = carry
+            check_tensor("episode_stats", "carry[0]", cr, f32, (Cn,), device=self.device)
+            check_tensor("episode_stats", "carry[1]", cl, i32, (Cn,), device=self.device)
+        nb = _abi.EPISODE_STATS_BYTES
+        e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+        if out is None:
+            out = (e((Cn, nb), u8), e((int(classes), nb), u8) if summary else None, e((T, Cn), f32) if planes else None,
+                   e((T, Cn), i32) if planes else None)
+        if len(out) != 4:
+            raise ValueError("episode_stats: `out` is (col_stats, summary or None, episode_return or None, episode_len or None)")
+        col, summ, eret, elen = out
+        check_tensor("episode_stats", "out[0]", col, u8, (Cn, nb), align=16, device=self.device)
+        if summ is not None:
+            check_tensor("episode_stats", "out[1]", summ, u8, (int(classes), nb), align=16, device=self.device)
+        if eret is not None:
+            check_tensor("episode_stats", "out[2]", eret, f32, (T, Cn), align=16, device=self.device)
+        if elen is not None:
+            check_tensor("episode_stats", "out[3]", elen, i32, (T, Cn), align=16, device=self.device)
+        io = _abi.PhxEpisodeIO(T=T, G=int(group), N=N, K=int(classes), reward=_ptr(rewards), truncated=_ptr(truncations),
+                               terminated=_ptr(terminations), acted=_ptr(acted), reward_valid=_ptr(reward_valid), carry_return=_ptr(cr),
+                               carry_len=_ptr(cl), episode_return=_ptr(eret), episode_len=_ptr(elen), col_stats=_ptr(col),
+                               summary=_ptr(summ))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_episode_stats(C.byref(io), self._stream()), "phx_episode_stats")
+        return col, summ, eret, elen
+
     def compact(self, keep, planes, capacity=None, out=None):
         """``(start, out_row, out_col, {name: dense tensor})``: the kept elements of time-major planes, dense and in (column, row) =
         (env instance, agent, step) order, on the current stream (phx_traj_compact, include/phantom_amd_compact.h) -- the hole rows of

@@ -421,7 +421,7 @@ class PhantomEnv:
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
                gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False,
-               n_step=None):
+               n_step=None, episode_stats=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -484,7 +484,13 @@ class PhantomEnv:
         ``truncateds`` / ``new_obs``; on an FSM / Stackelberg env they are ``trajectory_rewards`` and the four ``trajectory_`` fields, a chain
         runs over the rows where the agent acted and never folds an incomplete transition into an earlier row.  A chain stops at a done
         flag and at the fragment's end.  The one-step fields and columns stay as they are; with ``compact=True`` the five columns are
-        compacted with the rest."""
+        compacted with the rest.
+
+        ``episode_stats``: a ``phantom_amd.EpisodeStats`` of this env.  None: nothing of this runs.  Otherwise its ``update`` sees the
+        fragment's time-major planes before any transpose or compaction -- rewards and flags, on an FSM / Stackelberg env with who
+        acted and ``reward_valid`` -- in every mode above, and its ``result()`` gives RLlib's ``episode_reward_mean`` / ``min`` /
+        ``max``, ``episode_len_mean`` and ``episodes_this_iter`` over the episodes that ended, also those an earlier call began.  The
+        returned batch is the one the call returns without the keyword."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -570,6 +576,8 @@ class PhantomEnv:
             done += n
             piece_ends.append(done - 1)
         self._episodes_done = ep
+        if episode_stats is not None:                            # (on the time-major planes; it does not wait)
+            episode_stats.update(dev, rew, trunc, term, acted, rvalid)
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device
         if compact:
             cols = {}                                            # (no transpose: the time-major planes go to DeviceEnv.compact below)
