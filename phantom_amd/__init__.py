@@ -34,4 +34,5 @@ from .distributed import all_gather_trajectory, make_sharded_env, shard_batch
 from .device import DeviceEnv            # DeviceEnv.gae / gae_masked / vtrace: a learner's targets of a fragment (include/phantom_amd_gae.h, _vtrace.h)
 from .rollout import FragmentBatch       # what PhantomEnv.sample returns (vf_preds / advantages / value_targets with value_fn=...)
 from .rollout import CompactFragment     # ... and with compact=True on FSM / Stackelberg envs: the kept rows only (include/phantom_amd_compact.h)
+from .batch import TrainBatcher         # sample(batcher=...): shuffled, standardized learner batches on the device (include/phantom_amd_batch.h)
 from .episodes import EpisodeStats       # sample(episode_stats=...): episode returns and lengths across fragments (include/phantom_amd_episodes.h)

@@ -192,6 +192,32 @@ class PhxEpisodeIO(C.Structure):
                                   "episode_return", "episode_len", "col_stats", "summary")]
 
 
+BATCH_MAX_PLANES = 32
+
+
+class PhxBatchPlane(C.Structure):
+    """phx_batch_plane (include/phantom_amd_batch.h): one plane of a phx_train_batch call"""
+    _fields_ = [("src", C.c_void_p), ("elem_bytes", C.c_int32), ("word_off", C.c_int32)]
+
+
+class PhxBatchMoments(C.Structure):
+    """phx_batch_moments (include/phantom_amd_batch.h): the moments of the standardized plane"""
+    _fields_ = [("count", C.c_int64), ("sum", C.c_double), ("sumsq", C.c_double), ("mean", C.c_float), ("den", C.c_float)]
+
+
+class PhxTrainBatchIO(C.Structure):
+    """phx_train_batch_io (include/phantom_amd_batch.h): the planes and buffers of one phx_train_batch call"""
+    _fields_ = [("T", C.c_int64), ("N", C.c_int64), ("capacity", C.c_int64), ("n_planes", C.c_int32), ("row_words", C.c_int32),
+                ("S", C.c_int32), ("class_id", C.c_int32), ("std_plane", C.c_int32), ("shuffle", C.c_int32), ("seed", C.c_uint64),
+                ("epoch", C.c_uint64)] + [(n, C.c_void_p) for n in ("keep", "col_class", "start", "records", "out_row", "out_col", "moments",
+                                                                    "workspace")] + [("reserved", C.c_int64 * 2),
+                                                                                     ("plane", PhxBatchPlane * BATCH_MAX_PLANES)]
+
+
+# the moments' 32 bytes as a numpy record: ndarray.view of a uint8 [32] host copy
+BATCH_MOMENTS_DTYPE = [("count", "<i8"), ("sum", "<f8"), ("sumsq", "<f8"), ("mean", "<f4"), ("den", "<f4")]
+BATCH_MOMENTS_BYTES = 32
+
 # the same 48 bytes as a numpy record: np.frombuffer / ndarray.view of a uint8 [.., 48] host copy of col_stats / summary
 EPISODE_STATS_DTYPE = [("count", "<i8"), ("len_sum", "<i8"), ("ret_sum", "<f8"), ("ret_sumsq", "<f8"), ("ret_min", "<f4"),
                        ("ret_max", "<f4"), ("len_min", "<i4"), ("len_max", "<i4")]
@@ -213,6 +239,11 @@ NSTEP_GATHER_KERNEL = "phx_nstep_gather_kernel"
 NSTEP_MAX_N = 64
 EPISODE_SCAN_KERNEL = "phx_episode_scan_kernel"          # (phx_episode_stats: the scan's name, with `summary` joined by "+" with the
 EPISODE_REDUCE_KERNEL = "phx_episode_reduce_kernel"      #  reduction's)
+BATCH_COUNT_KERNEL = "phx_batch_count_kernel"            # (phx_train_batch: the names of the kernels launched joined by "+"; the moments'
+BATCH_SCAN_KERNEL = "phx_batch_scan_kernel"              #  only with std_plane, the scatter's missing where it has nothing to write)
+BATCH_MOMENTS_KERNEL = "phx_batch_moments_kernel"
+BATCH_SCATTER_KERNEL = "phx_batch_scatter_kernel"
+BATCH_KERNELS = "+".join((BATCH_COUNT_KERNEL, BATCH_SCAN_KERNEL, BATCH_MOMENTS_KERNEL, BATCH_SCATTER_KERNEL))
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -227,6 +258,11 @@ assert C.sizeof(PhxEpisodeStats) == EPISODE_STATS_BYTES == 48      # (stated in 
 assert [getattr(PhxEpisodeStats, n).offset for n, _ in PhxEpisodeStats._fields_] == [0, 8, 16, 24, 32, 36, 40, 44]
 assert C.sizeof(PhxEpisodeIO) == 112
 assert [getattr(PhxEpisodeIO, n).offset for n, _ in PhxEpisodeIO._fields_] == [0, 4, 8, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96, 104]
+assert C.sizeof(PhxBatchPlane) == 16 and C.sizeof(PhxBatchMoments) == BATCH_MOMENTS_BYTES == 32      # (stated in include/phantom_amd_batch.h)
+assert C.sizeof(PhxTrainBatchIO) == 656
+assert [getattr(PhxTrainBatchIO, n).offset for n, _ in PhxTrainBatchIO._fields_] == [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 56, 64, 72, 80, 88, 96,
+                                                                                     104, 112, 120, 128, 144]
+assert [getattr(PhxBatchMoments, n).offset for n, _ in PhxBatchMoments._fields_] == [0, 8, 16, 24, 28]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -361,6 +397,13 @@ def bind_episode(lib):
     return lib
 
 
+def bind_batch(lib):
+    """restype / argtypes of include/phantom_amd_batch.h's entry point: libphantom_amd.so only, like bind_episode"""
+    lib.phx_train_batch.restype = C.c_int32
+    lib.phx_train_batch.argtypes = [C.POINTER(PhxTrainBatchIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -382,6 +425,7 @@ def load_library():
     bind_compact(lib)
     bind_nstep(lib)
     bind_episode(lib)
+    bind_batch(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

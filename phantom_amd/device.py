@@ -1029,6 +1029,103 @@ class DeviceEnv:
                 self._check(self.lib.phx_traj_compact(C.byref(io), self._stream()), "phx_traj_compact")
         return start, orow, ocol, dense
 
+    def train_batch(self, planes, keep=None, col_class=None, class_id: int = 0, standardize=None, shuffle: bool = True, seed: int = 0,
+                    epoch: int = 0, row_words=None, capacity=None, out=None, lead_dims=None):
+        """``(start, records, out_row, out_col, moments, layout)``: a learner's batch from time-major planes, on the current stream
+        (phx_train_batch, include/phantom_amd_batch.h) -- the kept elements in (env instance, agent, step) order, one class of
+        columns, one plane standardized, the rows shuffled by ``(seed, epoch)``, written as records: all columns of a row contiguous.
+        ``planes`` maps a name to a tensor ``[T, N..]`` (u8, f32, i32) or ``[T, N.., w]`` (f32, i32; w <= 64) on the env's device, at
+        most 32 of them; the leading shape ``[T, N..]`` is ``keep``'s (u8, != 0 keeps the element), without ``keep`` the first
+        ``lead_dims`` axes of the planes, and with neither the shape of the plane with the fewest dimensions.  ``col_class`` u8
+        ``[S]`` (S divides N) with ``class_id`` keeps the columns n with ``col_class[n % S] == class_id``.  ``standardize`` names an f32 plane without a trailing axis: its kept values leave as
+        ``(x - mean) / max(1e-4, std)``, and ``moments`` (uint8 ``[32]``, a record of ``_abi.BATCH_MOMENTS_DTYPE``) holds count, sum,
+        sumsq, mean and den.  ``layout[name] = (word_off, w, dtype)``: the plane's 32-bit words ``[word_off, word_off + w)`` of a
+        record (a u8 plane: one word, zero-extended); the planes are packed in order and ``row_words`` defaults to their words rounded
+        up to a multiple of 16, whole 64-byte units.  ``records`` is i32 ``[capacity, row_words]``, ``out_row`` / ``out_col`` i32
+        ``[capacity]`` (``capacity`` defaults to T * N), ``start`` i64 ``[N + 1]`` with K, the number of records, in ``start[N]``:
+        records ``[0, K)`` are written, or NOTHING but ``start`` and ``moments`` when K > capacity -- the caller compares; the call
+        does not synchronise.  ``out``: ``(start, records, out_row or None, out_col or None, moments, workspace)``, caller-owned and
+        16-byte aligned, ``workspace`` f64 ``[N, 2]``, the last two None without ``standardize``; allocated here when None."""
+        torch = _torch()
+        f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
+        planes = dict(planes)
+        if len(planes) > _abi.BATCH_MAX_PLANES:
+            raise ValueError(f"train_batch: {len(planes)} planes, at most {_abi.BATCH_MAX_PLANES} fit one call")
+        lead = keep if keep is not None else min((x for x in planes.values() if hasattr(x, "dim")), key=lambda x: x.dim(), default=None)
+        if lead is None or not hasattr(lead, "dim") or lead.dim() < 2:
+            raise ValueError("train_batch: `keep` or a plane must give the leading shape [T, B, S] (or [T, N])")
+        if keep is None and lead_dims is not None:
+            if isinstance(lead_dims, bool) or not isinstance(lead_dims, (int, np.integer)) or not 2 <= lead_dims <= lead.dim():
+                raise ValueError(f"train_batch: lead_dims = {lead_dims!r} must be an int in [2, {lead.dim()}]")
+            shape = tuple(lead.shape[:lead_dims])
+        else:
+            shape = tuple(lead.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"train_batch: the leading shape is {shape}: T and N must be >= 1")
+        if keep is not None:
+            check_tensor("train_batch", "keep", keep, u8, shape, device=self.device)
+        S = 1
+        if col_class is not None:
+            if not hasattr(col_class, "dim") or col_class.dim() != 1 or col_class.numel() < 1 or N % col_class.numel():
+                raise ValueError(f"train_batch: `col_class` must be a u8 [S] tensor with S >= 1 dividing the {N} columns")
+            S = col_class.numel()
+            check_tensor("train_batch", "col_class", col_class, u8, (S,), device=self.device)
+        if isinstance(class_id, bool) or not isinstance(class_id, (int, np.integer)) or not 0 <= class_id <= 255:
+            raise ValueError(f"train_batch: class_id = {class_id!r} must be an int in [0, 255]")
+        for name, v in (("seed", seed), ("epoch", epoch)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 64:
+                raise ValueError(f"train_batch: {name} = {v!r} must be an int in [0, 2^64)")
+        layout, off = {}, 0
+        for name, x in planes.items():
+            if x is None or not hasattr(x, "dim") or x.dim() not in (len(shape), len(shape) + 1):
+                raise ValueError(f"train_batch: plane `{name}` must be a {shape} or {shape + ('w',)} tensor")
+            tail = tuple(x.shape[len(shape):])
+            if tail and (x.dtype == u8 or not 1 <= tail[0] <= 64):
+                raise ValueError(f"train_batch: plane `{name}`: a trailing axis needs f32 or i32 and 1 <= w <= 64")
+            check_tensor("train_batch", f"plane `{name}`", x, (u8, f32, i32), shape + tail, device=self.device)
+            w = tail[0] if tail else 1
+            layout[name] = (off, w, x.dtype)
+            off += w
+        if row_words is None:
+            row_words = max(16, -(-off // 16) * 16)
+        if isinstance(row_words, bool) or not isinstance(row_words, (int, np.integer)) or not 4 <= row_words <= 256 or row_words % 4 or off > row_words:
+            raise ValueError(f"train_batch: row_words = {row_words!r} must be a multiple of 4 in [4, 256] that holds the planes' {off} words")
+        std_plane = -1
+        if standardize is not None:
+            if standardize not in planes or planes[standardize].dtype != f32 or planes[standardize].dim() != len(shape):
+                raise ValueError(f"train_batch: standardize = {standardize!r} must name an f32 plane without a trailing axis")
+            std_plane = list(planes).index(standardize)
+        capacity = T * N if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"train_batch: capacity = {capacity} must be >= 0")
+        e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+        if out is None:
+            out = (e((N + 1,), i64), e((capacity, int(row_words)), i32), e((capacity,), i32), e((capacity,), i32),
+                   e((_abi.BATCH_MOMENTS_BYTES,), u8) if std_plane >= 0 else None, e((N, 2), torch.float64) if std_plane >= 0 else None)
+        if len(out) != 6:
+            raise ValueError("train_batch: `out` is (start, records, out_row or None, out_col or None, moments or None, workspace or None)")
+        start, records, orow, ocol, moments, workspace = out
+        check_tensor("train_batch", "out[0]", start, i64, (N + 1,), align=16, device=self.device)
+        check_tensor("train_batch", "out[1]", records, i32, (capacity, int(row_words)), align=16, device=self.device)
+        for i, x in ((2, orow), (3, ocol)):
+            if x is not None:
+                check_tensor("train_batch", f"out[{i}]", x, i32, (capacity,), align=16, device=self.device)
+        if std_plane >= 0:
+            check_tensor("train_batch", "out[4]", moments, u8, (_abi.BATCH_MOMENTS_BYTES,), align=16, device=self.device)
+            check_tensor("train_batch", "out[5]", workspace, torch.float64, (N, 2), align=16, device=self.device)
+        elif moments is not None or workspace is not None:
+            raise ValueError("train_batch: `out[4]` (moments) and `out[5]` (workspace) need `standardize`")
+        io = _abi.PhxTrainBatchIO(T=T, N=N, capacity=capacity, n_planes=len(planes), row_words=int(row_words), S=S, class_id=int(class_id),
+                                  std_plane=std_plane, shuffle=1 if shuffle else 0, seed=int(seed), epoch=int(epoch), keep=_ptr(keep),
+                                  col_class=_ptr(col_class), start=_ptr(start), records=_ptr(records), out_row=_ptr(orow), out_col=_ptr(ocol),
+                                  moments=_ptr(moments), workspace=_ptr(workspace))
+        for k, (name, x) in enumerate(planes.items()):
+            io.plane[k] = _abi.PhxBatchPlane(src=_ptr(x), elem_bytes=x.element_size() * layout[name][1], word_off=layout[name][0])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_train_batch(C.byref(io), self._stream()), "phx_train_batch")
+        return start, records, orow, ocol, moments, layout
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

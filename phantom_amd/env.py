@@ -421,7 +421,7 @@ class PhantomEnv:
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
                gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False,
-               n_step=None, episode_stats=None):
+               n_step=None, episode_stats=None, batcher=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -490,7 +490,16 @@ class PhantomEnv:
         fragment's time-major planes before any transpose or compaction -- rewards and flags, on an FSM / Stackelberg env with who
         acted and ``reward_valid`` -- in every mode above, and its ``result()`` gives RLlib's ``episode_reward_mean`` / ``min`` /
         ``max``, ``episode_len_mean`` and ``episodes_this_iter`` over the episodes that ended, also those an earlier call began.  The
-        returned batch is the one the call returns without the keyword."""
+        returned batch is the one the call returns without the keyword.
+
+        ``batcher``: a ``phantom_amd.TrainBatcher`` of this env, for a torch learner on the same GPU.  None: nothing of this runs.
+        Otherwise everything above runs as it does without the keyword, on the time-major planes; then, in place of the transposes, the
+        compaction and the copies to the host, one ``DeviceEnv.train_batch`` call per policy (include/phantom_amd_batch.h) writes the
+        columns ``to_sample_batches()`` would emit for that mode -- the device planes among them: ``eps_id`` / ``agent_index`` / ``t`` /
+        ``env_id`` follow from a record's row and column, ``action_prob`` from ``action_logp`` -- as shuffled records, with ``keep`` = who
+        acted on an FSM / Stackelberg env, ``advantages`` standardized over the policy's rows and the batcher's call counter as the
+        epoch.  The call returns ``{policy_id: phantom_amd.rollout.DeviceBatch}`` and copies nothing to the host; ``episode_stats``
+        works beside it, ``compact`` excludes it."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -513,6 +522,8 @@ class PhantomEnv:
                 raise ValueError("sample: `vtrace_clip` is (clip_rho_threshold, clip_c_threshold, clip_pg_rho_threshold)")
         dev = self._device()
         masked = self.spec.env_type != _abi.ENV_PLAIN            # per-agent trajectories with holes: validity planes, phx_gae_masked
+        if compact and batcher is not None:
+            raise ValueError("sample: `compact` and `batcher` exclude each other (the batcher drops the hole rows itself)")
         if compact and not masked:
             raise ValueError("sample: `compact` serves FSM / Stackelberg envs only (on a plain env every agent acts in every step: there "
                              "is no row to drop)")
@@ -579,6 +590,13 @@ class PhantomEnv:
         if episode_stats is not None:                            # (on the time-major planes; it does not wait)
             episode_stats.update(dev, rew, trunc, term, acted, rvalid)
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device
+        tm = None                                                # with a batcher: the time-major planes under their column names
+        if batcher is not None:
+            am = lambda x: None                                  # (no transpose: the time-major planes go to the batcher below)
+            tm = {"obs": obs, "new_obs": new_obs, "actions": (raw if explore else act).unsqueeze(-1), "rewards": rew, "terminateds": term,
+                  "truncateds": trunc}
+            if explore:
+                tm.update(action_logp=logp, action_dist_inputs=dist)
         if compact:
             cols = {}                                            # (no transpose: the time-major planes go to DeviceEnv.compact below)
         else:
@@ -609,13 +627,19 @@ class PhantomEnv:
             if target_logp_fn is not None:
                 vs, pg = dev.vtrace(rew, trunc, vf, logp, tl, vf_next, term, gamma, lambda_, *vtrace_clip)
                 cols.update(vf_preds=am(vf), target_logp=am(tl), vtrace_vs=am(vs), vtrace_pg_advantages=am(pg))
+                if tm is not None:
+                    tm.update(vf_preds=vf, target_logp=tl, vtrace_vs=vs, vtrace_pg_advantages=pg)
             else:
                 adv, vt = dev.gae(rew, trunc, vf, vf_next, term, gamma, lambda_)
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
+                if tm is not None:
+                    tm.update(vf_preds=vf, advantages=adv, value_targets=vt)
         if n_step is not None and not masked:                    # the step-aligned planes are the transitions: every row complete
             ns = dev.nstep(rew, trunc, term, None, None, new_obs, int(n_step), gamma)
             cols.update(nstep_rewards=am(ns[0]), nstep_discounts=am(ns[1]), nstep_new_obs=am(ns[6]), nstep_terminateds=am(ns[3]),
                         nstep_truncateds=am(ns[4]))
+            if tm is not None:
+                tm.update(nstep_rewards=ns[0], nstep_discounts=ns[1], nstep_new_obs=ns[6], nstep_terminateds=ns[3], nstep_truncateds=ns[4])
         if masked:
             # the agent's own view of the other three transition columns, over gae_masked's segments (before it: last_kernel() stays its)
             nrow, nterm, ntrunc, nobs = dev.traj_next(trunc, term, acted, nvalid, obs, new_obs)
@@ -641,13 +665,15 @@ class PhantomEnv:
             if n_step is not None:                               # the agent's own transitions: gae_masked's rewards, traj_next's other columns
                 ns = dev.nstep(rs, ntrunc, nterm, acted, nrow, nobs, int(n_step), gamma)
                 ns = dict(nstep_rewards=ns[0], nstep_discounts=ns[1], nstep_new_obs=ns[6], nstep_terminateds=ns[3], nstep_truncateds=ns[4])
-            if compact:
+            if compact or batcher is not None:
                 planes = {"obs": obs, "new_obs": nobs, "actions": act, "rewards": rs, "terminateds": nterm, "truncateds": ntrunc,
                           "trajectory_next_row": nrow}
                 if value_fn is not None:
                     planes.update(vf_preds=vf, advantages=adv, value_targets=vt)
                 if ns is not None:
                     planes.update(ns)
+                if batcher is not None:
+                    return batcher.collect(dev, dict(planes, actions=act.unsqueeze(-1)), acted)
                 return self._compact_fragment(acted, planes, np.broadcast_to(t_in_ep, (B, T)).copy(),
                                               (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64))
             cols.update(trajectory_rewards=am(rs))
@@ -655,6 +681,8 @@ class PhantomEnv:
                 cols.update({k: am(x) for k, x in ns.items()})
             if value_fn is not None:
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
+        if batcher is not None:
+            return batcher.collect(dev, tm)
         host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         stage = np.concatenate(stages, axis=1) if stages and all(x is not None for x in stages) else None

@@ -410,7 +410,7 @@ class BatchedBaseEnv(_BaseEnvBase):
 
     def sample(self, T: int, actions=None, exo=None, policy_mapping_fn=None, policy=None, explore: bool = False, generator=None,
                value_fn=None, gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0),
-               compact: bool = False, n_step=None, episode_stats=None):
+               compact: bool = False, n_step=None, episode_stats=None, batcher=None):
         """The bulk exit: T steps of every env instance in fused device rollouts and the fragment as per-policy ``SampleBatch``
         column dicts (phantom_amd.rollout.FragmentBatch.to_sample_batches) -- no python object per (env, agent, step).
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
@@ -424,7 +424,13 @@ class BatchedBaseEnv(_BaseEnvBase):
         with the rows where the agent did not act dropped on the device before the copy to the host (PhantomEnv.sample).  ``n_step``: a
         replay learner's ``nstep_rewards`` / ``nstep_discounts`` / ``nstep_new_obs`` / ``nstep_terminateds`` / ``nstep_truncateds`` columns
         next to the one-step ones (PhantomEnv.sample).  ``episode_stats``: a ``phantom_amd.EpisodeStats`` that receives the fragment's
-        episode returns and lengths (PhantomEnv.sample); the columns stay as they are."""
+        episode returns and lengths (PhantomEnv.sample); the columns stay as they are.  ``batcher``: a ``phantom_amd.TrainBatcher`` built
+        with the policy mapping; the call then returns its ``{policy_id: DeviceBatch}`` on the device and ``policy_mapping_fn`` here
+        is not used (PhantomEnv.sample)."""
+        if batcher is not None:
+            return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
+                                   lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip, n_step=n_step,
+                                   episode_stats=episode_stats, batcher=batcher)
         return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
                                lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip,
                                compact=compact, n_step=n_step, episode_stats=episode_stats).to_sample_batches(policy_mapping_fn)
