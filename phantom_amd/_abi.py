@@ -214,6 +214,17 @@ class PhxTrainBatchIO(C.Structure):
                                                                                      ("plane", PhxBatchPlane * BATCH_MAX_PLANES)]
 
 
+class PhxSeqBatchIO(C.Structure):
+    """phx_seq_batch_io (include/phantom_amd_seq.h): the planes and buffers of one phx_seq_batch call"""
+    _fields_ = [("T", C.c_int64), ("N", C.c_int64), ("capacity", C.c_int64), ("n_planes", C.c_int32), ("row_words", C.c_int32),
+                ("S", C.c_int32), ("class_id", C.c_int32), ("std_plane", C.c_int32), ("shuffle", C.c_int32), ("seed", C.c_uint64),
+                ("epoch", C.c_uint64)] + [(n, C.c_void_p) for n in ("keep", "col_class", "seq_start", "records", "out_row", "out_col", "moments",
+                                                                    "workspace")] + [("max_seq_len", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("terminated", "truncated", "seq_lens", "seq_row", "seq_col")] + [("reserved", C.c_int64 * 2),
+                                                                                                          ("plane", PhxBatchPlane * BATCH_MAX_PLANES)]
+
+
+SEQ_MAX_LEN = 65536
 # the moments' 32 bytes as a numpy record: ndarray.view of a uint8 [32] host copy
 BATCH_MOMENTS_DTYPE = [("count", "<i8"), ("sum", "<f8"), ("sumsq", "<f8"), ("mean", "<f4"), ("den", "<f4")]
 BATCH_MOMENTS_BYTES = 32
@@ -244,6 +255,11 @@ BATCH_SCAN_KERNEL = "phx_batch_scan_kernel"              #  only with std_plane,
 BATCH_MOMENTS_KERNEL = "phx_batch_moments_kernel"
 BATCH_SCATTER_KERNEL = "phx_batch_scatter_kernel"
 BATCH_KERNELS = "+".join((BATCH_COUNT_KERNEL, BATCH_SCAN_KERNEL, BATCH_MOMENTS_KERNEL, BATCH_SCATTER_KERNEL))
+SEQ_COUNT_KERNEL = "phx_seq_count_kernel"                # (phx_seq_batch: as phx_train_batch's, the scatter's also missing where the three
+SEQ_SCAN_KERNEL = "phx_seq_scan_kernel"                  #  per-sequence outputs are not given either)
+SEQ_MOMENTS_KERNEL = "phx_seq_moments_kernel"
+SEQ_SCATTER_KERNEL = "phx_seq_scatter_kernel"
+SEQ_KERNELS = "+".join((SEQ_COUNT_KERNEL, SEQ_SCAN_KERNEL, SEQ_MOMENTS_KERNEL, SEQ_SCATTER_KERNEL))
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -263,6 +279,9 @@ assert C.sizeof(PhxTrainBatchIO) == 656
 assert [getattr(PhxTrainBatchIO, n).offset for n, _ in PhxTrainBatchIO._fields_] == [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 56, 64, 72, 80, 88, 96,
                                                                                      104, 112, 120, 128, 144]
 assert [getattr(PhxBatchMoments, n).offset for n, _ in PhxBatchMoments._fields_] == [0, 8, 16, 24, 28]
+assert C.sizeof(PhxSeqBatchIO) == 704                    # (stated in include/phantom_amd_seq.h)
+assert [getattr(PhxSeqBatchIO, n).offset for n, _ in PhxSeqBatchIO._fields_] == [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 56, 64, 72, 80, 88, 96, 104,
+                                                                                 112, 120, 128, 136, 144, 152, 160, 168, 176, 192]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -404,6 +423,13 @@ def bind_batch(lib):
     return lib
 
 
+def bind_seq(lib):
+    """restype / argtypes of include/phantom_amd_seq.h's entry point: libphantom_amd.so only, like bind_batch"""
+    lib.phx_seq_batch.restype = C.c_int32
+    lib.phx_seq_batch.argtypes = [C.POINTER(PhxSeqBatchIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -426,6 +452,7 @@ def load_library():
     bind_nstep(lib)
     bind_episode(lib)
     bind_batch(lib)
+    bind_seq(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -1029,6 +1029,60 @@ class DeviceEnv:
                 self._check(self.lib.phx_traj_compact(C.byref(io), self._stream()), "phx_traj_compact")
         return start, orow, ocol, dense
 
+    def _batch_planes(self, fn, planes, keep, col_class, class_id, standardize, seed, epoch, row_words, lead_dims):
+        """the arguments ``train_batch`` and ``seq_batch`` share, checked: ``(planes, shape, T, N, S, layout, row_words, std_plane)``"""
+        torch = _torch()
+        f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
+        planes = dict(planes)
+        if len(planes) > _abi.BATCH_MAX_PLANES:
+            raise ValueError(f"{fn}: {len(planes)} planes, at most {_abi.BATCH_MAX_PLANES} fit one call")
+        lead = keep if keep is not None else min((x for x in planes.values() if hasattr(x, "dim")), key=lambda x: x.dim(), default=None)
+        if lead is None or not hasattr(lead, "dim") or lead.dim() < 2:
+            raise ValueError(f"{fn}: `keep` or a plane must give the leading shape [T, B, S] (or [T, N])")
+        if keep is None and lead_dims is not None:
+            if isinstance(lead_dims, bool) or not isinstance(lead_dims, (int, np.integer)) or not 2 <= lead_dims <= lead.dim():
+                raise ValueError(f"{fn}: lead_dims = {lead_dims!r} must be an int in [2, {lead.dim()}]")
+            shape = tuple(lead.shape[:lead_dims])
+        else:
+            shape = tuple(lead.shape)
+        T, N = shape[0], int(np.prod(shape[1:]))
+        if T < 1 or N < 1:
+            raise ValueError(f"{fn}: the leading shape is {shape}: T and N must be >= 1")
+        if keep is not None:
+            check_tensor(fn, "keep", keep, u8, shape, device=self.device)
+        S = 1
+        if col_class is not None:
+            if not hasattr(col_class, "dim") or col_class.dim() != 1 or col_class.numel() < 1 or N % col_class.numel():
+                raise ValueError(f"{fn}: `col_class` must be a u8 [S] tensor with S >= 1 dividing the {N} columns")
+            S = col_class.numel()
+            check_tensor(fn, "col_class", col_class, u8, (S,), device=self.device)
+        if isinstance(class_id, bool) or not isinstance(class_id, (int, np.integer)) or not 0 <= class_id <= 255:
+            raise ValueError(f"{fn}: class_id = {class_id!r} must be an int in [0, 255]")
+        for name, v in (("seed", seed), ("epoch", epoch)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 64:
+                raise ValueError(f"{fn}: {name} = {v!r} must be an int in [0, 2^64)")
+        layout, off = {}, 0
+        for name, x in planes.items():
+            if x is None or not hasattr(x, "dim") or x.dim() not in (len(shape), len(shape) + 1):
+                raise ValueError(f"{fn}: plane `{name}` must be a {shape} or {shape + ('w',)} tensor")
+            tail = tuple(x.shape[len(shape):])
+            if tail and (x.dtype == u8 or not 1 <= tail[0] <= 64):
+                raise ValueError(f"{fn}: plane `{name}`: a trailing axis needs f32 or i32 and 1 <= w <= 64")
+            check_tensor(fn, f"plane `{name}`", x, (u8, f32, i32), shape + tail, device=self.device)
+            w = tail[0] if tail else 1
+            layout[name] = (off, w, x.dtype)
+            off += w
+        if row_words is None:
+            row_words = max(16, -(-off // 16) * 16)
+        if isinstance(row_words, bool) or not isinstance(row_words, (int, np.integer)) or not 4 <= row_words <= 256 or row_words % 4 or off > row_words:
+            raise ValueError(f"{fn}: row_words = {row_words!r} must be a multiple of 4 in [4, 256] that holds the planes' {off} words")
+        std_plane = -1
+        if standardize is not None:
+            if standardize not in planes or planes[standardize].dtype != f32 or planes[standardize].dim() != len(shape):
+                raise ValueError(f"{fn}: standardize = {standardize!r} must name an f32 plane without a trailing axis")
+            std_plane = list(planes).index(standardize)
+        return planes, shape, T, N, S, layout, int(row_words), std_plane
+
     def train_batch(self, planes, keep=None, col_class=None, class_id: int = 0, standardize=None, shuffle: bool = True, seed: int = 0,
                     epoch: int = 0, row_words=None, capacity=None, out=None, lead_dims=None):
         """``(start, records, out_row, out_col, moments, layout)``: a learner's batch from time-major planes, on the current stream
@@ -1048,54 +1102,8 @@ class DeviceEnv:
         16-byte aligned, ``workspace`` f64 ``[N, 2]``, the last two None without ``standardize``; allocated here when None."""
         torch = _torch()
         f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
-        planes = dict(planes)
-        if len(planes) > _abi.BATCH_MAX_PLANES:
-            raise ValueError(f"train_batch: {len(planes)} planes, at most {_abi.BATCH_MAX_PLANES} fit one call")
-        lead = keep if keep is not None else min((x for x in planes.values() if hasattr(x, "dim")), key=lambda x: x.dim(), default=None)
-        if lead is None or not hasattr(lead, "dim") or lead.dim() < 2:
-            raise ValueError("train_batch: `keep` or a plane must give the leading shape [T, B, S] (or [T, N])")
-        if keep is None and lead_dims is not None:
-            if isinstance(lead_dims, bool) or not isinstance(lead_dims, (int, np.integer)) or not 2 <= lead_dims <= lead.dim():
-                raise ValueError(f"train_batch: lead_dims = {lead_dims!r} must be an int in [2, {lead.dim()}]")
-            shape = tuple(lead.shape[:lead_dims])
-        else:
-            shape = tuple(lead.shape)
-        T, N = shape[0], int(np.prod(shape[1:]))
-        if T < 1 or N < 1:
-            raise ValueError(f"train_batch: the leading shape is {shape}: T and N must be >= 1")
-        if keep is not None:
-            check_tensor("train_batch", "keep", keep, u8, shape, device=self.device)
-        S = 1
-        if col_class is not None:
-            if not hasattr(col_class, "dim") or col_class.dim() != 1 or col_class.numel() < 1 or N % col_class.numel():
-                raise ValueError(f"train_batch: `col_class` must be a u8 [S] tensor with S >= 1 dividing the {N} columns")
-            S = col_class.numel()
-            check_tensor("train_batch", "col_class", col_class, u8, (S,), device=self.device)
-        if isinstance(class_id, bool) or not isinstance(class_id, (int, np.integer)) or not 0 <= class_id <= 255:
-            raise ValueError(f"train_batch: class_id = {class_id!r} must be an int in [0, 255]")
-        for name, v in (("seed", seed), ("epoch", epoch)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 64:
-                raise ValueError(f"train_batch: {name} = {v!r} must be an int in [0, 2^64)")
-        layout, off = {}, 0
-        for name, x in planes.items():
-            if x is None or not hasattr(x, "dim") or x.dim() not in (len(shape), len(shape) + 1):
-                raise ValueError(f"train_batch: plane `{name}` must be a {shape} or {shape + ('w',)} tensor")
-            tail = tuple(x.shape[len(shape):])
-            if tail and (x.dtype == u8 or not 1 <= tail[0] <= 64):
-                raise ValueError(f"train_batch: plane `{name}`: a trailing axis needs f32 or i32 and 1 <= w <= 64")
-            check_tensor("train_batch", f"plane `{name}`", x, (u8, f32, i32), shape + tail, device=self.device)
-            w = tail[0] if tail else 1
-            layout[name] = (off, w, x.dtype)
-            off += w
-        if row_words is None:
-            row_words = max(16, -(-off // 16) * 16)
-        if isinstance(row_words, bool) or not isinstance(row_words, (int, np.integer)) or not 4 <= row_words <= 256 or row_words % 4 or off > row_words:
-            raise ValueError(f"train_batch: row_words = {row_words!r} must be a multiple of 4 in [4, 256] that holds the planes' {off} words")
-        std_plane = -1
-        if standardize is not None:
-            if standardize not in planes or planes[standardize].dtype != f32 or planes[standardize].dim() != len(shape):
-                raise ValueError(f"train_batch: standardize = {standardize!r} must name an f32 plane without a trailing axis")
-            std_plane = list(planes).index(standardize)
+        planes, shape, T, N, S, layout, row_words, std_plane = self._batch_planes("train_batch", planes, keep, col_class, class_id, standardize,
+                                                                                  seed, epoch, row_words, lead_dims)
         capacity = T * N if capacity is None else int(capacity)
         if capacity < 0:
             raise ValueError(f"train_batch: capacity = {capacity} must be >= 0")
@@ -1125,6 +1133,69 @@ class DeviceEnv:
         with torch.cuda.device(self.device):
             self._check(self.lib.phx_train_batch(C.byref(io), self._stream()), "phx_train_batch")
         return start, records, orow, ocol, moments, layout
+
+    def seq_batch(self, planes, max_seq_len, keep=None, terminated=None, truncated=None, col_class=None, class_id: int = 0, standardize=None,
+                  shuffle: bool = True, seed: int = 0, epoch: int = 0, row_words=None, capacity=None, out=None, lead_dims=None):
+        """``(seq_start, records, seq_lens, seq_row, seq_col, out_row, out_col, moments, layout)``: a recurrent learner's batch from
+        time-major planes, on the current stream (phx_seq_batch, include/phantom_amd_seq.h) -- ``train_batch``'s kept elements, every
+        column's kept rows cut into sequences at a set ``terminated`` / ``truncated`` flag (u8 of the leading shape, read at kept
+        elements only; None: all zero) and every ``max_seq_len`` = L rows, each sequence zero-padded to L, one plane standardized over
+        the kept rows and the SEQUENCES shuffled by ``(seed, epoch)``.  ``planes``, ``keep``, ``col_class`` / ``class_id``,
+        ``standardize``, ``row_words``, ``lead_dims`` and ``layout`` are ``train_batch``'s.  ``capacity`` counts sequences and defaults
+        to N * ceil(T / L) without flag planes and to T * N (every row could close a sequence) with one.  ``records`` is i32 ``[capacity, L, row_words]``,
+        ``out_row`` / ``out_col`` i32 ``[capacity, L]`` (-1 in padding), ``seq_lens`` / ``seq_row`` / ``seq_col`` i32 ``[capacity]``
+        (a sequence's rows, its first fragment row and its column), ``seq_start`` i64 ``[N + 1]`` with Q, the number of sequences,
+        in ``seq_start[N]``: sequences ``[0, Q)`` are written, or NOTHING but ``seq_start`` and ``moments`` when Q > capacity -- the
+        caller compares; the call does not synchronise.  ``out``: ``(seq_start, records, seq_lens or None, seq_row or None, seq_col or
+        None, out_row or None, out_col or None, moments, workspace)``, caller-owned and 16-byte aligned, ``workspace`` f64 ``[3, N]``,
+        the last two None without ``standardize``; allocated here when None."""
+        torch = _torch()
+        f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
+        if isinstance(max_seq_len, bool) or not isinstance(max_seq_len, (int, np.integer)) or not 1 <= max_seq_len <= _abi.SEQ_MAX_LEN:
+            raise ValueError(f"seq_batch: max_seq_len = {max_seq_len!r} must be an int in [1, {_abi.SEQ_MAX_LEN}]")
+        L = int(max_seq_len)
+        planes, shape, T, N, S, layout, row_words, std_plane = self._batch_planes("seq_batch", planes, keep, col_class, class_id, standardize,
+                                                                                  seed, epoch, row_words, lead_dims)
+        for name, x in (("terminated", terminated), ("truncated", truncated)):
+            if x is not None:
+                check_tensor("seq_batch", name, x, u8, shape, device=self.device)
+        if capacity is None:                                     # (the length cuts, and a flag per row where flags are given)
+            capacity = N * -(-T // L) if terminated is None and truncated is None else T * N
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise ValueError(f"seq_batch: capacity = {capacity!r} must be an int >= 0")
+        capacity = int(capacity)
+        e = lambda s, dtype: torch.empty(s, dtype=dtype, device=self.device)
+        if out is None:
+            out = (e((N + 1,), i64), e((capacity, L, int(row_words)), i32), e((capacity,), i32), e((capacity,), i32), e((capacity,), i32),
+                   e((capacity, L), i32), e((capacity, L), i32), e((_abi.BATCH_MOMENTS_BYTES,), u8) if std_plane >= 0 else None,
+                   e((3, N), torch.float64) if std_plane >= 0 else None)
+        if len(out) != 9:
+            raise ValueError("seq_batch: `out` is (seq_start, records, seq_lens or None, seq_row or None, seq_col or None, out_row or None, "
+                             "out_col or None, moments or None, workspace or None)")
+        start, records, lens, srow, scol, orow, ocol, moments, workspace = out
+        check_tensor("seq_batch", "out[0]", start, i64, (N + 1,), align=16, device=self.device)
+        check_tensor("seq_batch", "out[1]", records, i32, (capacity, L, int(row_words)), align=16, device=self.device)
+        for i, x in ((2, lens), (3, srow), (4, scol)):
+            if x is not None:
+                check_tensor("seq_batch", f"out[{i}]", x, i32, (capacity,), align=16, device=self.device)
+        for i, x in ((5, orow), (6, ocol)):
+            if x is not None:
+                check_tensor("seq_batch", f"out[{i}]", x, i32, (capacity, L), align=16, device=self.device)
+        if std_plane >= 0:
+            check_tensor("seq_batch", "out[7]", moments, u8, (_abi.BATCH_MOMENTS_BYTES,), align=16, device=self.device)
+            check_tensor("seq_batch", "out[8]", workspace, torch.float64, (3, N), align=16, device=self.device)
+        elif moments is not None or workspace is not None:
+            raise ValueError("seq_batch: `out[7]` (moments) and `out[8]` (workspace) need `standardize`")
+        io = _abi.PhxSeqBatchIO(T=T, N=N, capacity=capacity, n_planes=len(planes), row_words=int(row_words), S=S, class_id=int(class_id),
+                                std_plane=std_plane, shuffle=1 if shuffle else 0, seed=int(seed), epoch=int(epoch), keep=_ptr(keep),
+                                col_class=_ptr(col_class), seq_start=_ptr(start), records=_ptr(records), out_row=_ptr(orow), out_col=_ptr(ocol),
+                                moments=_ptr(moments), workspace=_ptr(workspace), max_seq_len=L, terminated=_ptr(terminated),
+                                truncated=_ptr(truncated), seq_lens=_ptr(lens), seq_row=_ptr(srow), seq_col=_ptr(scol))
+        for k, (name, x) in enumerate(planes.items()):
+            io.plane[k] = _abi.PhxBatchPlane(src=_ptr(x), elem_bytes=x.element_size() * layout[name][1], word_off=layout[name][0])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_seq_batch(C.byref(io), self._stream()), "phx_seq_batch")
+        return start, records, lens, srow, scol, orow, ocol, moments, layout
 
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable

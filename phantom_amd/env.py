@@ -499,7 +499,10 @@ class PhantomEnv:
         ``env_id`` follow from a record's row and column, ``action_prob`` from ``action_logp`` -- as shuffled records, with ``keep`` = who
         acted on an FSM / Stackelberg env, ``advantages`` standardized over the policy's rows and the batcher's call counter as the
         epoch.  The call returns ``{policy_id: phantom_amd.rollout.DeviceBatch}`` and copies nothing to the host; ``episode_stats``
-        works beside it, ``compact`` excludes it."""
+        works beside it, ``compact`` excludes it.  A batcher built with ``max_seq_len=L`` (a recurrent or attention learner) makes one
+        ``DeviceEnv.seq_batch`` call per policy instead (include/phantom_amd_seq.h) and the call returns ``{policy_id:
+        phantom_amd.rollout.DeviceSeqBatch}``: every agent's rows in time order, cut at the ``terminateds`` / ``truncateds`` columns
+        above and every L rows, zero-padded to L, with ``seq_lens`` and each sequence's first row and column, the sequences shuffled."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:

@@ -425,8 +425,9 @@ class BatchedBaseEnv(_BaseEnvBase):
         replay learner's ``nstep_rewards`` / ``nstep_discounts`` / ``nstep_new_obs`` / ``nstep_terminateds`` / ``nstep_truncateds`` columns
         next to the one-step ones (PhantomEnv.sample).  ``episode_stats``: a ``phantom_amd.EpisodeStats`` that receives the fragment's
         episode returns and lengths (PhantomEnv.sample); the columns stay as they are.  ``batcher``: a ``phantom_amd.TrainBatcher`` built
-        with the policy mapping; the call then returns its ``{policy_id: DeviceBatch}`` on the device and ``policy_mapping_fn`` here
-        is not used (PhantomEnv.sample)."""
+        with the policy mapping; the call then returns its ``{policy_id: DeviceBatch}`` on the device -- with
+        ``TrainBatcher(max_seq_len=L)`` its ``{policy_id: DeviceSeqBatch}`` of padded, shuffled sequences -- and ``policy_mapping_fn``
+        here is not used (PhantomEnv.sample)."""
         if batcher is not None:
             return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
                                    lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip, n_step=n_step,

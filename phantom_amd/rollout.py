@@ -24,7 +24,7 @@ from typing import Any, Callable, Dict, Iterable, List, Mapping, Optional, Tuple
 
 import numpy as np
 
-from .batch import DeviceBatch  # noqa: F401  (sample(batcher=...)'s result: records on the device, next to the two host forms)
+from .batch import DeviceBatch, DeviceSeqBatch  # noqa: F401  (sample(batcher=...)'s results: records on the device, next to the two host forms)
 
 DEFAULT_POLICY_ID = "default_policy"          # ray.rllib.policy.sample_batch.DEFAULT_POLICY_ID
 

@@ -129,6 +129,119 @@ def measure(lib, _abi, torch, np, T, seconds, repeats, dev):
     return dict(T=T, N=N, K=K, sets=n_sets, bytes=one, us=us)
 
 
+SEQ_TORCH = "phx_train_batch(shuffle=0) + torch: chop, pad, randperm"
+
+
+def make_seq_set(torch, _abi, lib, T, N, L, gen, dev, stream):
+    s = make_set(torch, _abi, T, N, gen, dev)
+    for name in ("terminateds", "truncateds"):            # an episode end about every 50 kept rows
+        s["planes"][name].copy_((torch.rand((T, N), generator=gen, device=dev) < 0.01).to(torch.uint8))
+    s["io"].shuffle = 0                                   # the other path's first step: records in (column, row) order
+    e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    start, moments, workspace = e((N + 1,), torch.int64), e((32,), torch.uint8), e((3, N), torch.float64)
+    io = _abi.PhxSeqBatchIO(T=T, N=N, capacity=0, n_planes=len(COLUMNS), row_words=ROW_WORDS, S=1, class_id=0,
+                            std_plane=[c[0] for c in COLUMNS].index("advantages"), shuffle=1, seed=1, epoch=0, keep=s["keep"].data_ptr(),
+                            max_seq_len=L, terminated=s["planes"]["terminateds"].data_ptr(), truncated=s["planes"]["truncateds"].data_ptr(),
+                            seq_start=start.data_ptr(), moments=moments.data_ptr(), workspace=workspace.data_ptr())
+    for i in range(len(COLUMNS)):
+        io.plane[i] = s["io"].plane[i]
+    if lib.phx_seq_batch(C.byref(io), stream) != 0:        # capacity 0: the count alone, for Q
+        raise RuntimeError(lib.phx_last_error().decode())
+    Q = int(start[N])
+    out = dict(records=e((Q, L, ROW_WORDS), torch.int32), out_row=e((Q, L), torch.int32), out_col=e((Q, L), torch.int32), seq_lens=e((Q,), torch.int32),
+               seq_row=e((Q,), torch.int32), seq_col=e((Q,), torch.int32))
+    io.capacity = Q
+    for k, v in out.items():
+        setattr(io, k, v.data_ptr())
+    s.update(seq_io=io, seq_out=out, seq_start=start, Q=Q, seq_moments=moments, seq_workspace=workspace)
+    return s
+
+
+def seq_in_torch(torch, lib, s, K, L, stream):
+    """the parent's path to the same sequences"""
+    if lib.phx_train_batch(C.byref(s["io"]), stream) != 0:
+        raise RuntimeError(lib.phx_last_error().decode())
+    Q = s["Q"]
+    rec, row, col = s["out"]["records"][:K], s["out"]["out_row"][:K], s["out"]["out_col"][:K]
+    flag = (rec[:, s["layout"]["terminateds"][0]] != 0) | (rec[:, s["layout"]["truncateds"][0]] != 0)
+    e = torch.arange(K, device=rec.device)
+    brk = torch.ones(K, dtype=torch.bool, device=rec.device)
+    brk[1:] = (col[1:] != col[:-1]) | flag[:-1]
+    i = (e - torch.cummax(torch.where(brk, e, 0), 0).values) % L
+    opens = i == 0
+    sid = torch.cumsum(opens, 0) - 1
+    perm = torch.randperm(Q, device=rec.device)
+    sigma = perm.index_select(0, sid)
+    slot = sigma * L + i
+    records = torch.zeros((Q * L, ROW_WORDS), dtype=torch.int32, device=rec.device).index_copy_(0, slot, rec)
+    orow = torch.full((Q * L,), -1, dtype=torch.int32, device=rec.device).index_copy_(0, slot, row)
+    ocol = torch.full((Q * L,), -1, dtype=torch.int32, device=rec.device).index_copy_(0, slot, col)
+    lens = torch.zeros(Q, dtype=torch.int32, device=rec.device).index_add_(0, sigma, torch.ones((), dtype=torch.int32, device=rec.device).expand(K))
+    orow, ocol = orow.view(Q, L), ocol.view(Q, L)
+    return dict(records=records.view(Q, L, ROW_WORDS), out_row=orow, out_col=ocol, seq_lens=lens, seq_row=orow[:, 0], seq_col=ocol[:, 0])
+
+
+def seq_expected_bytes(T, N, Q, L):
+    return (46 + 3 + 7) * T * N + (4 * ROW_WORDS + 8) * Q * L + 12 * Q
+
+
+def measure_seq(lib, _abi, torch, np, T, L, seconds, repeats, dev):
+    N = B * S
+    K = (T + 1) // 2 * N
+    gen = torch.Generator(device=dev).manual_seed(0)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sets = [make_seq_set(torch, _abi, lib, T, N, L, gen, dev, stream)]
+    one = seq_expected_bytes(T, N, sets[0]["Q"], L)
+    n_sets = max(2, -(-(256 << 20) // one) + 1)           # working set beyond the 256 MiB Infinity Cache
+    sets += [make_seq_set(torch, _abi, lib, T, N, L, gen, dev, stream) for _ in range(n_sets - 1)]
+    refs = [C.byref(s["seq_io"]) for s in sets]
+
+    def call(i):
+        if lib.phx_seq_batch(refs[i % n_sets], stream) != 0:
+            raise RuntimeError(lib.phx_last_error().decode())
+
+    calls = {"phx_seq_batch": call, SEQ_TORCH: lambda i: seq_in_torch(torch, lib, sets[i % n_sets], K, L, stream)}
+    s = sets[0]
+    call(0)
+    want = seq_in_torch(torch, lib, s, K, L, stream)
+    torch.cuda.synchronize()
+    Q, got = s["Q"], s["seq_out"]
+    assert int(s["seq_start"][N]) == Q and int(s["out"]["start"][N]) == K and int(got["seq_lens"].sum()) == K
+    oa = torch.argsort(got["seq_col"].long() * T + got["seq_row"].long())
+    ob = torch.argsort(want["seq_col"].long() * T + want["seq_row"].long())
+    if not all(bool((got[k][oa] == want[k][ob]).all()) for k in got):
+        raise RuntimeError(f"the call and the torch path disagree (T = {T})")
+    for i in range(n_sets):
+        call(i)
+    us = {k: [] for k in calls}
+    for _ in range(repeats):                              # alternating
+        for k, fn in calls.items():
+            us[k].append(window(fn, seconds, torch))
+    return dict(T=T, N=N, K=K, Q=Q, L=L, sets=n_sets, bytes=one, us=us)
+
+
+def report_seq(rows, torch, np):
+    L = rows[0]["L"]
+    out = ["phx_seq_batch against phx_train_batch(shuffle = 0) + a torch chop-pad-shuffle for the same sequences, and the bytes it needs",
+           f"(tools/batch_time.py --seq {L}); B = 4 096, S = 9, D = 3 (SC64's shape, N = 36 864 columns), alternating keep (K = T N / 2), the",
+           f"9-column PPO set in 16-word records, flags at 1 % of the elements per plane, max_seq_len = {L}, capacity = Q, advantages standardized,",
+           "sequences shuffled, all six outputs written.  Expected bytes: 56 T N in, 72 Q L + 12 Q out.  One process, alternating, buffer sets",
+           "rotated; median [min .. max] over the repeats, microseconds per call; TB/s = the expected bytes over the median.  The torch path is",
+           "handed K and Q (no host wait).  Checked against that path before timing.",
+           f"device: {torch.cuda.get_device_name()}", ""]
+    for r in rows:
+        med = {k: float(np.median(v)) for k, v in r["us"].items()}
+        out.append(f"T = {r['T']:3d}  ({r['T'] * r['N'] / 1e6:.2f} M elements, K = {r['K'] / 1e6:.2f} M rows in Q = {r['Q'] / 1e6:.3f} M sequences = "
+                   f"{r['Q'] * r['L'] / 1e6:.2f} M slots, {r['sets']} buffer sets of {r['bytes'] / 1e6:.1f} MB)")
+        for k, v in r["us"].items():
+            v = np.array(v)
+            out.append(f"    {k:62s} {med[k]:10.1f} us  [{v.min():.1f} .. {v.max():.1f}]  spread {(v.max() - v.min()) / med[k]:.3f}")
+        a = med["phx_seq_batch"]
+        out.append(f"    the call: {r['bytes'] / 1e6:.2f} MB expected, {r['bytes'] / a / 1e6:.3f} TB/s = {r['bytes'] / (a * 1e-6) / PEAK_BYTES_PER_S:.3f} of the peak;  "
+                   f"the torch path takes {med[SEQ_TORCH] / a:.2f}x")
+    return "\n".join(out) + "\n"
+
+
 def report(rows, torch, np):
     out = ["phx_train_batch against phx_traj_compact + torch for the same batch, and the bytes it needs (tools/batch_time.py); B = 4 096, S = 9,",
            "D = 3 (SC64's shape, N = 36 864 columns), alternating keep (K = T N / 2), the 9-column PPO set in 16-word records, advantages",
@@ -153,6 +266,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--seq", type=int, default=None, metavar="L", help="time phx_seq_batch with max_seq_len = L instead (profiles/seq_time.txt)")
     ap.add_argument("--rows", type=int, nargs="+", default=list(TS), help="the T values (one of them alone: a kernel trace of that shape)")
     args = ap.parse_args()
     import numpy as np
@@ -164,6 +278,14 @@ if __name__ == "__main__":
     lib = _abi.load_library()
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = []
+    if args.seq is not None:
+        for T in args.rows:
+            rows.append(measure_seq(lib, _abi, torch, np, T, args.seq, args.seconds, args.repeats, dev))
+            torch.cuda.empty_cache()
+            print(report_seq(rows[-1:], torch, np).split("\n", 8)[-1], flush=True)
+        with open(args.out or os.path.join(ROOT, "profiles", "seq_time.txt"), "w") as f:
+            f.write(report_seq(rows, torch, np))
+        sys.exit(0)
     for T in args.rows:
         rows.append(measure(lib, _abi, torch, np, T, args.seconds, args.repeats, dev))
         torch.cuda.empty_cache()
