@@ -36,3 +36,4 @@ from .rollout import FragmentBatch       # what PhantomEnv.sample returns (vf_pr
 from .rollout import CompactFragment     # ... and with compact=True on FSM / Stackelberg envs: the kept rows only (include/phantom_amd_compact.h)
 from .batch import TrainBatcher         # sample(batcher=...): shuffled, standardized learner batches on the device (include/phantom_amd_batch.h)
 from .episodes import EpisodeStats       # sample(episode_stats=...): episode returns and lengths across fragments (include/phantom_amd_episodes.h)
+from .replay import ReplayBuffer        # sample(batcher=..., replay=...): a device ring of records with uniform sampling (include/phantom_amd_replay.h)

@@ -224,7 +224,27 @@ class PhxSeqBatchIO(C.Structure):
                                                                                                           ("plane", PhxBatchPlane * BATCH_MAX_PLANES)]
 
 
+class PhxReplayState(C.Structure):
+    """phx_replay_state (include/phantom_amd_replay.h): the 32 device-resident bytes that go with a ring"""
+    _fields_ = [("cursor", C.c_int64), ("size", C.c_int64), ("total", C.c_int64), ("refused", C.c_int64)]
+
+
+class PhxReplayAddIO(C.Structure):
+    """phx_replay_add_io (include/phantom_amd_replay.h): the buffers of one phx_replay_add call"""
+    _fields_ = [("capacity", C.c_int64), ("src_capacity", C.c_int64), ("count", C.c_int64), ("row_words", C.c_int32), ("reserved0", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("count_ptr", "src", "ring", "state")] + [("reserved", C.c_int64 * 2)]
+
+
+class PhxReplaySampleIO(C.Structure):
+    """phx_replay_sample_io (include/phantom_amd_replay.h): the buffers of one phx_replay_sample call"""
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("row_words", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64),
+                ("draw", C.c_uint64)] + [(n, C.c_void_p) for n in ("slot_in", "ring", "state", "out", "out_slot")] + [("reserved", C.c_int64 * 2)]
+
+
 SEQ_MAX_LEN = 65536
+# the state's 32 bytes as a numpy record: ndarray.view of an int64 [4] host copy
+REPLAY_STATE_DTYPE = [("cursor", "<i8"), ("size", "<i8"), ("total", "<i8"), ("refused", "<i8")]
+REPLAY_STATE_BYTES = 32
 # the moments' 32 bytes as a numpy record: ndarray.view of a uint8 [32] host copy
 BATCH_MOMENTS_DTYPE = [("count", "<i8"), ("sum", "<f8"), ("sumsq", "<f8"), ("mean", "<f4"), ("den", "<f4")]
 BATCH_MOMENTS_BYTES = 32
@@ -260,6 +280,10 @@ SEQ_SCAN_KERNEL = "phx_seq_scan_kernel"                  #  per-sequence outputs
 SEQ_MOMENTS_KERNEL = "phx_seq_moments_kernel"
 SEQ_SCATTER_KERNEL = "phx_seq_scatter_kernel"
 SEQ_KERNELS = "+".join((SEQ_COUNT_KERNEL, SEQ_SCAN_KERNEL, SEQ_MOMENTS_KERNEL, SEQ_SCATTER_KERNEL))
+REPLAY_ADD_KERNEL = "phx_replay_add_kernel"              # (phx_replay_add: the copy, then the one-thread commit of the state)
+REPLAY_COMMIT_KERNEL = "phx_replay_commit_kernel"
+REPLAY_ADD_KERNELS = "+".join((REPLAY_ADD_KERNEL, REPLAY_COMMIT_KERNEL))
+REPLAY_SAMPLE_KERNEL = "phx_replay_sample_kernel"
 MAX_FRAGMENTS = 8
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
@@ -282,6 +306,10 @@ assert [getattr(PhxBatchMoments, n).offset for n, _ in PhxBatchMoments._fields_]
 assert C.sizeof(PhxSeqBatchIO) == 704                    # (stated in include/phantom_amd_seq.h)
 assert [getattr(PhxSeqBatchIO, n).offset for n, _ in PhxSeqBatchIO._fields_] == [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 56, 64, 72, 80, 88, 96, 104,
                                                                                  112, 120, 128, 136, 144, 152, 160, 168, 176, 192]
+assert C.sizeof(PhxReplayState) == REPLAY_STATE_BYTES == 32      # (stated in include/phantom_amd_replay.h, as is every offset below)
+assert C.sizeof(PhxReplayAddIO) == 80 and C.sizeof(PhxReplaySampleIO) == 96
+assert [getattr(PhxReplayAddIO, n).offset for n, _ in PhxReplayAddIO._fields_] == [0, 8, 16, 24, 28, 32, 40, 48, 56, 64]
+assert [getattr(PhxReplaySampleIO, n).offset for n, _ in PhxReplaySampleIO._fields_] == [0, 8, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -430,6 +458,15 @@ def bind_seq(lib):
     return lib
 
 
+def bind_replay(lib):
+    """restype / argtypes of include/phantom_amd_replay.h's entry points: libphantom_amd.so only, like bind_seq"""
+    lib.phx_replay_add.restype = C.c_int32
+    lib.phx_replay_add.argtypes = [C.POINTER(PhxReplayAddIO), C.c_void_p]
+    lib.phx_replay_sample.restype = C.c_int32
+    lib.phx_replay_sample.argtypes = [C.POINTER(PhxReplaySampleIO), C.c_void_p]
+    return lib
+
+
 def load_library():
     """Load libphantom_amd.so (built in-tree by ``phantom_amd.build``); never falls back."""
     global _LIB
@@ -453,6 +490,7 @@ def load_library():
     bind_episode(lib)
     bind_batch(lib)
     bind_seq(lib)
+    bind_replay(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)

@@ -1197,6 +1197,79 @@ class DeviceEnv:
             self._check(self.lib.phx_seq_batch(C.byref(io), self._stream()), "phx_seq_batch")
         return start, records, lens, srow, scol, orow, ocol, moments, layout
 
+    def _replay_ring(self, fn, ring, state):
+        """the arguments ``replay_add`` and ``replay_sample`` share, checked: ``(C, row_words)``"""
+        torch = _torch()
+        if ring is None or not hasattr(ring, "dim") or ring.dim() != 2 or ring.shape[0] < 1:
+            raise ValueError(f"{fn}: `ring` must be an i32 [C, row_words] tensor with C >= 1")
+        Cn, row_words = int(ring.shape[0]), int(ring.shape[1])
+        if not 4 <= row_words <= 256 or row_words % 4:
+            raise ValueError(f"{fn}: `ring` has records of {row_words} words: row_words must be a multiple of 4 in [4, 256]")
+        check_tensor(fn, "ring", ring, torch.int32, (Cn, row_words), align=16, device=self.device)
+        check_tensor(fn, "state", state, torch.int64, (4,), align=16, device=self.device)
+        return Cn, row_words
+
+    def replay_add(self, ring, state, records, count=None):
+        """Append records to a ring on the current stream (phx_replay_add, include/phantom_amd_replay.h).  ``ring`` is i32
+        ``[C, row_words]`` and ``state`` i64 ``[4]`` (cursor, size, total, refused; zero-filled once: the empty ring), both 16-byte
+        aligned on the env's device; ``records`` i32 ``[src_capacity, row_words]``, a ``DeviceBatch``'s.  ``count``: None for all of
+        ``records``, an int K in ``[0, src_capacity]``, or a device i64 tensor of one element that holds K (``batch.start[-1:]``) --
+        read on the device, the call does not synchronise: a K outside ``[0, src_capacity]`` adds nothing and counts in
+        ``state[3]``.  The last ``min(K, C)`` of the first K records go to the slots from the cursor on, wrapping."""
+        torch = _torch()
+        Cn, row_words = self._replay_ring("replay_add", ring, state)
+        if records is None or not hasattr(records, "dim") or records.dim() != 2:
+            raise ValueError(f"replay_add: `records` must be an i32 [src_capacity, {row_words}] tensor")
+        src_capacity = int(records.shape[0])
+        check_tensor("replay_add", "records", records, torch.int32, (src_capacity, row_words), align=16, device=self.device)
+        count_ptr, host_count = None, 0
+        if count is None:
+            host_count = src_capacity
+        elif hasattr(count, "dim"):
+            if count.numel() != 1:
+                raise ValueError(f"replay_add: a device `count` must hold one element, got shape {tuple(count.shape)}")
+            check_tensor("replay_add", "count", count, torch.int64, tuple(count.shape), align=8, device=self.device)
+            count_ptr = count
+        else:
+            if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 0 <= count <= src_capacity:
+                raise ValueError(f"replay_add: count = {count!r} must be None, a device i64 tensor or an int in [0, {src_capacity}]")
+            host_count = int(count)
+        io = _abi.PhxReplayAddIO(capacity=Cn, src_capacity=src_capacity, count=host_count, row_words=row_words, count_ptr=_ptr(count_ptr),
+                                 src=_ptr(records) if src_capacity else None, ring=_ptr(ring), state=_ptr(state))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_replay_add(C.byref(io), self._stream()), "phx_replay_add")
+
+    def replay_sample(self, ring, state, n, seed: int = 0, draw: int = 0, slots=None, out=None):
+        """``(out, out_slot)``: n records of a ring on the current stream (phx_replay_sample, include/phantom_amd_replay.h) --
+        ``out`` i32 ``[n, row_words]`` and ``out_slot`` i64 ``[n]``, the slot every record came from.  ``ring`` / ``state`` are
+        ``replay_add``'s.  Without ``slots`` the slots are uniform draws with replacement from the valid ones, stream ``(seed,
+        draw)``; with ``slots`` (a device i64 ``[n]`` tensor) they are the caller's, as a prioritized sampler needs.  A slot outside
+        ``[0, size)`` -- every one while the ring is empty -- gives a record of zeros and -1.  ``out``: ``(out, out_slot or None)``,
+        caller-owned and 16-byte aligned; allocated here when None.  The call does not synchronise."""
+        torch = _torch()
+        Cn, row_words = self._replay_ring("replay_sample", ring, state)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"replay_sample: n = {n!r} must be an int >= 1")
+        n = int(n)
+        for name, v in (("seed", seed), ("draw", draw)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 64:
+                raise ValueError(f"replay_sample: {name} = {v!r} must be an int in [0, 2^64)")
+        if slots is not None:
+            check_tensor("replay_sample", "slots", slots, torch.int64, (n,), align=8, device=self.device)
+        if out is None:
+            out = (torch.empty((n, row_words), dtype=torch.int32, device=self.device), torch.empty((n,), dtype=torch.int64, device=self.device))
+        if len(out) != 2:
+            raise ValueError("replay_sample: `out` is (out, out_slot or None)")
+        rec, oslot = out
+        check_tensor("replay_sample", "out[0]", rec, torch.int32, (n, row_words), align=16, device=self.device)
+        if oslot is not None:
+            check_tensor("replay_sample", "out[1]", oslot, torch.int64, (n,), align=16, device=self.device)
+        io = _abi.PhxReplaySampleIO(capacity=Cn, n=n, row_words=row_words, seed=int(seed), draw=int(draw), slot_in=_ptr(slots), ring=_ptr(ring),
+                                    state=_ptr(state), out=_ptr(rec), out_slot=_ptr(oslot))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.phx_replay_sample(C.byref(io), self._stream()), "phx_replay_sample")
+        return rec, oslot
+
     def step_graph(self, actions=None, n: Optional[int] = None, policy=None, action_valid=None):
         """Capture ``n`` consecutive ``phx_step`` launches ONCE into a hipGraph and return a replayable
         ``StepGraph``: per-step launch cadence drops from the host's ~6-9 us to the graph's.

@@ -419,9 +419,16 @@ class PhantomEnv:
         self._obs_state = ("traj", traj.last_obs, None if traj.obs_valid is None else traj.obs_valid[T - 1])
         return traj
 
+    @staticmethod
+    def _replay_add(batches, replay):
+        """``sample(batcher=..., replay=...)``: every policy's batch into its buffer; the batches are returned as they are"""
+        for pid, rb in (replay or {}).items():
+            rb.add(batches[pid])
+        return batches
+
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
                gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False,
-               n_step=None, episode_stats=None, batcher=None):
+               n_step=None, episode_stats=None, batcher=None, replay=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -502,7 +509,14 @@ class PhantomEnv:
         works beside it, ``compact`` excludes it.  A batcher built with ``max_seq_len=L`` (a recurrent or attention learner) makes one
         ``DeviceEnv.seq_batch`` call per policy instead (include/phantom_amd_seq.h) and the call returns ``{policy_id:
         phantom_amd.rollout.DeviceSeqBatch}``: every agent's rows in time order, cut at the ``terminateds`` / ``truncateds`` columns
-        above and every L rows, zero-padded to L, with ``seq_lens`` and each sequence's first row and column, the sequences shuffled."""
+        above and every L rows, zero-padded to L, with ``seq_lens`` and each sequence's first row and column, the sequences shuffled.
+
+        ``replay``: a replay learner's buffer on the same GPU (DQN / SAC / TD3 / DDPG, usually next to ``n_step``).  None: nothing of
+        this runs.  A ``phantom_amd.ReplayBuffer`` with a one-policy ``batcher``, else a dict of them with exactly the batcher's policy
+        ids: after the batcher's calls every policy's records are appended to its ring with one ``DeviceEnv.replay_add`` call
+        (include/phantom_amd_replay.h), the number of records read on the device where the host does not know it -- no wait, no copy.
+        The call returns what it returns without the keyword; ``rb.sample(n)`` then draws a learner's minibatch from everything the
+        ring holds.  ``replay`` without ``batcher``, or with a ``max_seq_len`` batcher: ValueError."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -512,6 +526,9 @@ class PhantomEnv:
                 raise ValueError(f"sample: n_step = {n_step!r} must be None or an int in [1, {_abi.NSTEP_MAX_N}]")
             if not 0.0 <= float(np.float32(gamma)) <= 1.0:
                 raise ValueError(f"sample: n_step folds rewards with gamma = {gamma}, which must lie in [0, 1]")
+        if replay is not None:
+            from .replay import check_replay
+            replay = check_replay(replay, batcher)
         if explore and (policy is None or not policy.stochastic):
             raise ValueError("sample: explore=True needs a stochastic policy (a (mean, log_std) head or MLPPolicy(log_std=...))")
         if target_logp_fn is not None:
@@ -676,7 +693,7 @@ class PhantomEnv:
                 if ns is not None:
                     planes.update(ns)
                 if batcher is not None:
-                    return batcher.collect(dev, dict(planes, actions=act.unsqueeze(-1)), acted)
+                    return self._replay_add(batcher.collect(dev, dict(planes, actions=act.unsqueeze(-1)), acted), replay)
                 return self._compact_fragment(acted, planes, np.broadcast_to(t_in_ep, (B, T)).copy(),
                                               (eps[None, :] * B + np.arange(B)[:, None]).astype(np.int64))
             cols.update(trajectory_rewards=am(rs))
@@ -685,7 +702,7 @@ class PhantomEnv:
             if value_fn is not None:
                 cols.update(vf_preds=am(vf), advantages=am(adv), value_targets=am(vt))
         if batcher is not None:
-            return batcher.collect(dev, tm)
+            return self._replay_add(batcher.collect(dev, tm), replay)
         host = self._to_pinned(cols)
         ids = [self.spec.agent_ids[a] for a in self.spec.strategic_idx]
         stage = np.concatenate(stages, axis=1) if stages and all(x is not None for x in stages) else None
