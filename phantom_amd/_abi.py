@@ -399,71 +399,20 @@ def bind_signatures(lib):
     return lib
 
 
-def bind_gae(lib):
-    """restype / argtypes of include/phantom_amd_gae.h's entry points: libphantom_amd.so only (the CPU restatement behind
-    phantom_amd.h's symbols has no such functions, so this is not part of bind_signatures)"""
-    lib.phx_gae.restype = C.c_int32
-    lib.phx_gae.argtypes = [C.POINTER(PhxGaeIO), C.c_void_p]
-    lib.phx_gae_masked.restype = C.c_int32
-    lib.phx_gae_masked.argtypes = [C.POINTER(PhxGaeMaskedIO), C.c_void_p]
-    return lib
+# the learner-side entry points over fragments: each takes (its io struct *, stream) and returns a status (FragmentOps._launch)
+FRAGMENT_OPS = {"phx_gae": PhxGaeIO, "phx_gae_masked": PhxGaeMaskedIO, "phx_vtrace": PhxVtraceIO, "phx_traj_next": PhxTrajNextIO,
+                "phx_traj_compact": PhxTrajCompactIO, "phx_nstep": PhxNstepIO, "phx_episode_stats": PhxEpisodeIO,
+                "phx_train_batch": PhxTrainBatchIO, "phx_seq_batch": PhxSeqBatchIO, "phx_replay_add": PhxReplayAddIO,
+                "phx_replay_sample": PhxReplaySampleIO}
 
 
-def bind_vtrace(lib):
-    """restype / argtypes of include/phantom_amd_vtrace.h's entry point: libphantom_amd.so only, like bind_gae"""
-    lib.phx_vtrace.restype = C.c_int32
-    lib.phx_vtrace.argtypes = [C.POINTER(PhxVtraceIO), C.c_void_p]
-    return lib
-
-
-def bind_traj(lib):
-    """restype / argtypes of include/phantom_amd_traj.h's entry point: libphantom_amd.so only, like bind_vtrace"""
-    lib.phx_traj_next.restype = C.c_int32
-    lib.phx_traj_next.argtypes = [C.POINTER(PhxTrajNextIO), C.c_void_p]
-    return lib
-
-
-def bind_compact(lib):
-    """restype / argtypes of include/phantom_amd_compact.h's entry point: libphantom_amd.so only, like bind_traj"""
-    lib.phx_traj_compact.restype = C.c_int32
-    lib.phx_traj_compact.argtypes = [C.POINTER(PhxTrajCompactIO), C.c_void_p]
-    return lib
-
-
-def bind_nstep(lib):
-    """restype / argtypes of include/phantom_amd_nstep.h's entry point: libphantom_amd.so only, like bind_compact"""
-    lib.phx_nstep.restype = C.c_int32
-    lib.phx_nstep.argtypes = [C.POINTER(PhxNstepIO), C.c_void_p]
-    return lib
-
-
-def bind_episode(lib):
-    """restype / argtypes of include/phantom_amd_episodes.h's entry point: libphantom_amd.so only, like bind_nstep"""
-    lib.phx_episode_stats.restype = C.c_int32
-    lib.phx_episode_stats.argtypes = [C.POINTER(PhxEpisodeIO), C.c_void_p]
-    return lib
-
-
-def bind_batch(lib):
-    """restype / argtypes of include/phantom_amd_batch.h's entry point: libphantom_amd.so only, like bind_episode"""
-    lib.phx_train_batch.restype = C.c_int32
-    lib.phx_train_batch.argtypes = [C.POINTER(PhxTrainBatchIO), C.c_void_p]
-    return lib
-
-
-def bind_seq(lib):
-    """restype / argtypes of include/phantom_amd_seq.h's entry point: libphantom_amd.so only, like bind_batch"""
-    lib.phx_seq_batch.restype = C.c_int32
-    lib.phx_seq_batch.argtypes = [C.POINTER(PhxSeqBatchIO), C.c_void_p]
-    return lib
-
-
-def bind_replay(lib):
-    """restype / argtypes of include/phantom_amd_replay.h's entry points: libphantom_amd.so only, like bind_seq"""
-    lib.phx_replay_add.restype = C.c_int32
-    lib.phx_replay_add.argtypes = [C.POINTER(PhxReplayAddIO), C.c_void_p]
-    lib.phx_replay_sample.restype = C.c_int32
-    lib.phx_replay_sample.argtypes = [C.POINTER(PhxReplaySampleIO), C.c_void_p]
+def bind_fragment_ops(lib):
+    """restype / argtypes of the entry points of include/phantom_amd_{gae,vtrace,traj,compact,nstep,episodes,batch,seq,replay}.h:
+    libphantom_amd.so only (the CPU restatement behind phantom_amd.h's symbols has no such functions, so this is not part of
+    bind_signatures)"""
+    for entry, io in FRAGMENT_OPS.items():
+        getattr(lib, entry).restype = C.c_int32
+        getattr(lib, entry).argtypes = [C.POINTER(io), C.c_void_p]
     return lib
 
 
@@ -482,15 +431,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     bind_signatures(lib)
-    bind_gae(lib)
-    bind_vtrace(lib)
-    bind_traj(lib)
-    bind_compact(lib)
-    bind_nstep(lib)
-    bind_episode(lib)
-    bind_batch(lib)
-    bind_seq(lib)
-    bind_replay(lib)
+    bind_fragment_ops(lib)
     if lib.phx_abi_version() != ABI_VERSION:
         raise RuntimeError("libphantom_amd.so ABI version mismatch")
     _check_arch(torch)
