@@ -48,7 +48,7 @@
  * calls did not produce gives undefined results; the kernels still clamp what they read from it, size to [0, C] and cursor mod C, so
  * they never index outside `ring`.
  *
- * Out of scope: prioritized sampling (slot_in / out_slot are its building block: the caller draws the slots), sampling without
+ * Out of scope: prioritized sampling (slot_in / out_slot are its building block: phantom_amd_prio.h draws the slots), sampling without
  * replacement, sequence batches, spilling to the host, more than one GPU.
  * (tests/replay_ref.py, tests/test_replay_cpu.py, tests/test_gpu_replay.py)
  */

@@ -241,7 +241,59 @@ class PhxReplaySampleIO(C.Structure):
                 ("draw", C.c_uint64)] + [(n, C.c_void_p) for n in ("slot_in", "ring", "state", "out", "out_slot")] + [("reserved", C.c_int64 * 2)]
 
 
+class PhxPrioState(C.Structure):
+    """phx_prio_state (include/phantom_amd_prio.h): the 32 device-resident bytes that go with a priority tree"""
+    _fields_ = [("max_priority", C.c_float), ("reserved0", C.c_uint32), ("ignored", C.c_int64), ("refused", C.c_int64), ("reserved1", C.c_int64)]
+
+
+class PhxPrioAddIO(C.Structure):
+    """phx_prio_add_io (include/phantom_amd_prio.h): the buffers of one phx_prio_add call"""
+    _fields_ = [("capacity", C.c_int64), ("src_capacity", C.c_int64), ("count", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("count_ptr", "ring_state", "tree", "state")] + [("reserved", C.c_int64 * 2)]
+
+
+class PhxPrioUpdateIO(C.Structure):
+    """phx_prio_update_io (include/phantom_amd_prio.h): the buffers of one phx_prio_update call"""
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("slot_in", "priority", "ring_state", "tree", "state")] + [("reserved", C.c_int64 * 2)]
+
+
+class PhxPrioSampleIO(C.Structure):
+    """phx_prio_sample_io (include/phantom_amd_prio.h): the buffers of one phx_prio_sample call"""
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("seed", C.c_uint64), ("draw", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("ring_state", "tree", "out_slot", "out_priority")] + [("reserved", C.c_int64 * 2)]
+
+
 SEQ_MAX_LEN = 65536
+# the priority state's 32 bytes as a numpy record: ndarray.view of a uint8 [32] host copy
+PRIO_STATE_DTYPE = [("max_priority", "<f4"), ("reserved0", "<u4"), ("ignored", "<i8"), ("refused", "<i8"), ("reserved1", "<i8")]
+PRIO_STATE_BYTES = 32
+PRIO_FANOUT = 16
+PRIO_MAX_CAPACITY = 2 ** 30
+PRIO_TOP_NODES = 256                                     # levels of more nodes are served by one launch each, the others by the top kernel
+
+
+def prio_layout(capacity):
+    """``(L, offsets, W, words)`` of the tree over a ring of ``capacity`` slots (include/phantom_amd_prio.h): sum level l starts at
+    ``offsets[l]``, min level l >= 1 at ``W + offsets[l] - offsets[1]`` (``offsets[1]`` is w_0; L == 0: there is none), and the
+    buffer holds ``words`` f32"""
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= PRIO_MAX_CAPACITY:
+        raise ValueError(f"prio_layout: capacity = {capacity!r} must be an int in [1, 2^30]")
+    n, offsets = capacity, [0]
+    while n != 1:
+        w = PRIO_FANOUT * -(-n // PRIO_FANOUT)
+        offsets.append(offsets[-1] + w)
+        n = w // PRIO_FANOUT
+    W = offsets[-1] + PRIO_FANOUT
+    return len(offsets) - 1, tuple(offsets), W, 2 * W - PRIO_FANOUT * -(-capacity // PRIO_FANOUT)
+
+
+def prio_min_root(capacity):
+    """the word of the tree buffer that holds pmin, the root of the min tree (L == 0: the one leaf)"""
+    L, offsets, W, _ = prio_layout(capacity)
+    return W + offsets[L] - offsets[1] if L else 0
+
+
 # the state's 32 bytes as a numpy record: ndarray.view of an int64 [4] host copy
 REPLAY_STATE_DTYPE = [("cursor", "<i8"), ("size", "<i8"), ("total", "<i8"), ("refused", "<i8")]
 REPLAY_STATE_BYTES = 32
@@ -284,7 +336,23 @@ REPLAY_ADD_KERNEL = "phx_replay_add_kernel"              # (phx_replay_add: the 
 REPLAY_COMMIT_KERNEL = "phx_replay_commit_kernel"
 REPLAY_ADD_KERNELS = "+".join((REPLAY_ADD_KERNEL, REPLAY_COMMIT_KERNEL))
 REPLAY_SAMPLE_KERNEL = "phx_replay_sample_kernel"
+PRIO_FILL_KERNEL = "phx_prio_fill_kernel"                # (phx_prio_add / phx_prio_update: the names joined by "+"; the span's and the path's,
+PRIO_SPAN_KERNEL = "phx_prio_span_kernel"                #  one launch per level of more than 256 nodes, are missing for C <= 4096:
+PRIO_ZERO_KERNEL = "phx_prio_zero_kernel"                #  prio_kernels(names, C))
+PRIO_RAISE_KERNEL = "phx_prio_raise_kernel"
+PRIO_PATH_KERNEL = "phx_prio_path_kernel"
+PRIO_TOP_KERNEL = "phx_prio_top_kernel"
+PRIO_ADD_KERNELS = "+".join((PRIO_FILL_KERNEL, PRIO_SPAN_KERNEL, PRIO_TOP_KERNEL))
+PRIO_UPDATE_KERNELS = "+".join((PRIO_ZERO_KERNEL, PRIO_RAISE_KERNEL, PRIO_PATH_KERNEL, PRIO_TOP_KERNEL))
+PRIO_SAMPLE_KERNEL = "phx_prio_sample_kernel"
 MAX_FRAGMENTS = 8
+
+
+def prio_kernels(names, capacity):
+    """what phx_last_kernel() reads after a phx_prio_add / phx_prio_update call on a tree of ``capacity`` slots: ``PRIO_ADD_KERNELS`` /
+    ``PRIO_UPDATE_KERNELS`` without the per-level kernel where no level has more than 256 nodes"""
+    sparse = capacity > PRIO_FANOUT * PRIO_TOP_NODES
+    return "+".join(k for k in names.split("+") if sparse or k not in (PRIO_SPAN_KERNEL, PRIO_PATH_KERNEL))
 RH_ACTIONS_IN_DOMAIN, RH_EXO_IN_DOMAIN = 2, 4      # phx_rollout_io.hints
 
 
@@ -310,6 +378,12 @@ assert C.sizeof(PhxReplayState) == REPLAY_STATE_BYTES == 32      # (stated in in
 assert C.sizeof(PhxReplayAddIO) == 80 and C.sizeof(PhxReplaySampleIO) == 96
 assert [getattr(PhxReplayAddIO, n).offset for n, _ in PhxReplayAddIO._fields_] == [0, 8, 16, 24, 28, 32, 40, 48, 56, 64]
 assert [getattr(PhxReplaySampleIO, n).offset for n, _ in PhxReplaySampleIO._fields_] == [0, 8, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80]
+assert C.sizeof(PhxPrioState) == PRIO_STATE_BYTES == 32          # (stated in include/phantom_amd_prio.h, as is every offset below)
+assert [getattr(PhxPrioState, n).offset for n, _ in PhxPrioState._fields_] == [0, 4, 8, 16, 24]
+assert C.sizeof(PhxPrioAddIO) == 72 and C.sizeof(PhxPrioUpdateIO) == 72 and C.sizeof(PhxPrioSampleIO) == 80
+assert [getattr(PhxPrioAddIO, n).offset for n, _ in PhxPrioAddIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
+assert [getattr(PhxPrioUpdateIO, n).offset for n, _ in PhxPrioUpdateIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
+assert [getattr(PhxPrioSampleIO, n).offset for n, _ in PhxPrioSampleIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56, 64]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -406,11 +480,15 @@ FRAGMENT_OPS = {"phx_gae": PhxGaeIO, "phx_gae_masked": PhxGaeMaskedIO, "phx_vtra
                 "phx_replay_sample": PhxReplaySampleIO}
 
 
+# the entry points of include/phantom_amd_prio.h: the same calling convention, a table of their own
+PRIORITY_OPS = {"phx_prio_add": PhxPrioAddIO, "phx_prio_update": PhxPrioUpdateIO, "phx_prio_sample": PhxPrioSampleIO}
+
+
 def bind_fragment_ops(lib):
-    """restype / argtypes of the entry points of include/phantom_amd_{gae,vtrace,traj,compact,nstep,episodes,batch,seq,replay}.h:
+    """restype / argtypes of the entry points of include/phantom_amd_{gae,vtrace,traj,compact,nstep,episodes,batch,seq,replay,prio}.h:
     libphantom_amd.so only (the CPU restatement behind phantom_amd.h's symbols has no such functions, so this is not part of
     bind_signatures)"""
-    for entry, io in FRAGMENT_OPS.items():
+    for entry, io in {**FRAGMENT_OPS, **PRIORITY_OPS}.items():
         getattr(lib, entry).restype = C.c_int32
         getattr(lib, entry).argtypes = [C.POINTER(io), C.c_void_p]
     return lib

@@ -1,4 +1,4 @@
-"""FragmentOps: the learner-side entry points over time-major fragments (phx_gae .. phx_replay_sample), and their argument checks.
+"""FragmentOps: the learner-side entry points over time-major fragments (phx_gae .. phx_replay_sample, phx_prio_*), and their argument checks.
 
 None of them needs an env handle: a loaded library and a device are enough, and ``DeviceEnv`` inherits them.  The library
 receives raw device pointers, so every rule a tensor or a scalar has to meet is stated once here, as a helper or as a table the
@@ -89,7 +89,7 @@ class FragmentOps:
             raise DeviceError(f"{what} failed ({rc}): {self._err()}")
 
     def _launch(self, entry, io):
-        """one call of a fragment entry point (``_abi.FRAGMENT_OPS``) on torch's current stream of the device"""
+        """one call of a fragment entry point (``_abi.FRAGMENT_OPS``, ``_abi.PRIORITY_OPS``) on torch's current stream of the device"""
         torch = _torch()
         with torch.cuda.device(self.device):
             self._check(getattr(self.lib, entry)(C.byref(io), self._stream()), entry)
@@ -566,3 +566,70 @@ class FragmentOps:
             capacity=Cn, n=n, row_words=row_words, seed=seed, draw=draw, slot_in=_ptr(slots), ring=_ptr(ring), state=_ptr(state),
             out=_ptr(rec), out_slot=_ptr(oslot)))
         return rec, oslot
+
+    def _prio_tree(self, fn, tree, pstate, ring_state, capacity):
+        """the arguments the three ``prio_*`` calls share, checked: C"""
+        torch = _torch()
+        Cn = _int(fn, "capacity", capacity, 1, _abi.PRIO_MAX_CAPACITY, "an int in [1, 2^30]")
+        words = _abi.prio_layout(Cn)[3]
+        if tree is None or not hasattr(tree, "numel") or tree.numel() != words:
+            raise ValueError(f"{fn}: `tree` must be an f32 [{words}] tensor, _abi.prio_layout({Cn})'s words")
+        check_tensor(fn, "tree", tree, torch.float32, (words,), align=16, device=self.device)
+        check_tensor(fn, "pstate", pstate, torch.uint8, (_abi.PRIO_STATE_BYTES,), align=16, device=self.device)
+        check_tensor(fn, "ring_state", ring_state, torch.int64, (4,), align=8, device=self.device)
+        return Cn
+
+    def prio_add(self, tree, pstate, ring_state, capacity, src_capacity, count=None):
+        """Give the records the NEXT ``replay_add`` of the same batch will write the largest priority seen so far, on the current
+        stream (phx_prio_add, include/phantom_amd_prio.h).  ``tree`` is f32 ``[_abi.prio_layout(capacity).words]`` and ``pstate`` uint8
+        ``[32]`` (a record of ``_abi.PRIO_STATE_DTYPE``), both zero-filled once and 16-byte aligned on the env's device; ``ring_state``
+        is the ring's i64 ``[4]`` state, read only -- the call comes BEFORE the ring's add.  ``src_capacity`` and ``count`` are the
+        ring add's: the records the batch's buffer holds, and None for all of them, an int K in ``[0, src_capacity]`` or a device i64
+        tensor of one element that holds K.  A K outside ``[0, src_capacity]`` changes nothing and counts in the state's ``refused``."""
+        torch = _torch()
+        Cn = self._prio_tree("prio_add", tree, pstate, ring_state, capacity)
+        src_capacity = _int("prio_add", "src_capacity", src_capacity, 0)
+        count_ptr, host_count = None, 0
+        if count is None:
+            host_count = src_capacity
+        elif hasattr(count, "dim"):
+            if count.numel() != 1:
+                raise ValueError(f"prio_add: a device `count` must hold one element, got shape {tuple(count.shape)}")
+            check_tensor("prio_add", "count", count, torch.int64, tuple(count.shape), align=8, device=self.device)
+            count_ptr = count
+        else:
+            host_count = _int("prio_add", "count", count, 0, src_capacity, f"None, a device i64 tensor or an int in [0, {src_capacity}]")
+        self._launch("phx_prio_add", _abi.PhxPrioAddIO(
+            capacity=Cn, src_capacity=src_capacity, count=host_count, count_ptr=_ptr(count_ptr), ring_state=_ptr(ring_state), tree=_ptr(tree),
+            state=_ptr(pstate)))
+
+    def prio_update(self, tree, pstate, ring_state, capacity, slots, priorities):
+        """Set the priorities of sampled slots on the current stream (phx_prio_update, include/phantom_amd_prio.h): ``slots`` i64
+        ``[n]`` (a sample's ``.slots``) and ``priorities`` f32 ``[n]``, already raised to alpha, on the env's device; ``tree`` /
+        ``pstate`` / ``ring_state`` are ``prio_add``'s.  A slot outside the records held is ignored and counted in the state's
+        ``ignored``; a slot named more than once gets the largest of its priorities; NaN, zero and negatives become 2^-40."""
+        torch = _torch()
+        Cn = self._prio_tree("prio_update", tree, pstate, ring_state, capacity)
+        if slots is None or not hasattr(slots, "dim") or slots.dim() != 1 or slots.numel() < 1:
+            raise ValueError("prio_update: `slots` must be a device i64 [n] tensor with n >= 1")
+        n = int(slots.numel())
+        check_tensor("prio_update", "slots", slots, torch.int64, (n,), align=8, device=self.device)
+        check_tensor("prio_update", "priorities", priorities, torch.float32, (n,), device=self.device)
+        self._launch("phx_prio_update", _abi.PhxPrioUpdateIO(
+            capacity=Cn, n=n, slot_in=_ptr(slots), priority=_ptr(priorities), ring_state=_ptr(ring_state), tree=_ptr(tree), state=_ptr(pstate)))
+
+    def prio_sample(self, tree, pstate, ring_state, capacity, n, seed: int = 0, draw: int = 0, out=None):
+        """``(out_slot, out_priority)``: n slots drawn with replacement, each with probability priority / total, on the current
+        stream (phx_prio_sample, include/phantom_amd_prio.h) -- i64 ``[n]`` and f32 ``[n]``, the slot and its leaf; -1 and +0.0 while
+        nothing is held.  ``tree`` / ``pstate`` / ``ring_state`` are ``prio_add``'s (``pstate`` is checked, not read), the stream of
+        draws is ``(seed, draw)``.  ``replay_sample(slots=out_slot)`` gathers the records.  ``out``: the two tensors, caller-owned and
+        16-byte aligned; allocated here when None.  The call does not synchronise."""
+        torch = _torch()
+        Cn = self._prio_tree("prio_sample", tree, pstate, ring_state, capacity)
+        n = _int("prio_sample", "n", n, 1)
+        seed = _int("prio_sample", "seed", seed, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
+        draw = _int("prio_sample", "draw", draw, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
+        oslot, oprio = self._outputs("prio_sample", out, ((torch.int64, (n,), REQUIRED), (torch.float32, (n,), REQUIRED)), "(out_slot, out_priority)")
+        self._launch("phx_prio_sample", _abi.PhxPrioSampleIO(
+            capacity=Cn, n=n, seed=seed, draw=draw, ring_state=_ptr(ring_state), tree=_ptr(tree), out_slot=_ptr(oslot), out_priority=_ptr(oprio)))
+        return oslot, oprio
