@@ -100,3 +100,16 @@ batch = env.sample(100, policy=pol, explore=True, value_fn=critic, gamma=0.99, t
 cols = batch.to_sample_batches()["default_policy"]
 print("APPO batch:", cols["vtrace_vs"].shape[0], "rows from", env._device().last_kernel(), "| V-trace columns",
       sorted(k for k in cols if k.startswith("vtrace") or k in ("vf_preds", "target_logp", "action_logp")))
+
+# 10. a learner on the same GPU with RLlib's MeanStdFilter: the fragment never leaves the device.  `obs_filter=` normalises the obs /
+#     new_obs columns with the running statistics as they stood when the call began and then folds the call's raw observations in
+#     (include/phantom_amd_filter.h); `batcher=` turns the planes into shuffled records per policy.  Built with clip=None the filter
+#     folds into the device policy's first layer, so the fused rollout acts on raw observations under the same normalisation.
+obs_filter, batcher = ph.ObsFilter(env, clip=None), ph.TrainBatcher(env)
+learner_w, learner_b = list(pol.weights), list(pol.biases)      # the learner's parameters: they expect normalised observations
+for it in range(2):
+    w0, b0 = obs_filter.fold(learner_w, learner_b)              # (always from the learner's layer, never from a folded one)
+    pol.update([w0] + learner_w[1:], [b0] + learner_b[1:])
+    dbatch = env.sample(100, policy=pol, explore=True, value_fn=critic, obs_filter=obs_filter, batcher=batcher)["default_policy"]
+count, mean, var = obs_filter.stats()["default_policy"]
+print("filtered batch:", dbatch.count, "records on", dbatch.records.device, "| running mean", mean.round(2), "std", np.sqrt(var).round(2), "over", count)

@@ -38,3 +38,4 @@ from .batch import TrainBatcher         # sample(batcher=...): shuffled, standar
 from .episodes import EpisodeStats       # sample(episode_stats=...): episode returns and lengths across fragments (include/phantom_amd_episodes.h)
 from .replay import ReplayBuffer        # sample(batcher=..., replay=...): a device ring of records with uniform sampling (include/phantom_amd_replay.h)
 from .replay import PrioritizedReplayBuffer        # ... drawn by priority: a sum tree and a min tree next to the ring (include/phantom_amd_prio.h)
+from .obs_filter import ObsFilter          # sample(obs_filter=...): running mean / std observation normalisation on the device (include/phantom_amd_filter.h)

@@ -264,7 +264,36 @@ class PhxPrioSampleIO(C.Structure):
         (n, C.c_void_p) for n in ("ring_state", "tree", "out_slot", "out_priority")] + [("reserved", C.c_int64 * 2)]
 
 
+class PhxFilterState(C.Structure):
+    """phx_filter_state (include/phantom_amd_filter.h): the 272 device-resident bytes of one class of an observation filter"""
+    _fields_ = [("count", C.c_int64), ("updates", C.c_int64), ("mean", C.c_double * 16), ("m2", C.c_double * 16)]
+
+
+class PhxFilterUpdateIO(C.Structure):
+    """phx_filter_update_io (include/phantom_amd_filter.h): the buffers of one phx_filter_update call"""
+    _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("N", C.c_int64), ("n_classes", C.c_int32), ("reserved0", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("obs", "keep", "col_class", "state", "workspace")] + [("reserved", C.c_int64 * 2)]
+
+
+class PhxFilterApplyIO(C.Structure):
+    """phx_filter_apply_io (include/phantom_amd_filter.h): the buffers of one phx_filter_apply call"""
+    _fields_ = [("T", C.c_int32), ("D", C.c_int32), ("N", C.c_int64), ("n_classes", C.c_int32), ("clip", C.c_float)] + [
+        (n, C.c_void_p) for n in ("obs", "keep", "col_class", "state", "out")] + [("reserved", C.c_int64 * 2)]
+
+
 SEQ_MAX_LEN = 65536
+FILTER_MAX_DIM = 16
+FILTER_MAX_CLASSES = 16
+# one class's 272 bytes as a numpy record: ndarray.view of a uint8 [n_classes, 272] host copy
+FILTER_STATE_DTYPE = [("count", "<i8"), ("updates", "<i8"), ("mean", "<f8", (FILTER_MAX_DIM,)), ("m2", "<f8", (FILTER_MAX_DIM,))]
+FILTER_STATE_BYTES = 272
+
+
+def filter_workspace_bytes(N, D):
+    """PHX_FILTER_WORKSPACE_BYTES(N, D) of include/phantom_amd_filter.h: the scratch one phx_filter_update call needs"""
+    return 8 * ((int(D) + 1) * int(N) + 528)
+
+
 # the priority state's 32 bytes as a numpy record: ndarray.view of a uint8 [32] host copy
 PRIO_STATE_DTYPE = [("max_priority", "<f4"), ("reserved0", "<u4"), ("ignored", "<i8"), ("refused", "<i8"), ("reserved1", "<i8")]
 PRIO_STATE_BYTES = 32
@@ -345,6 +374,13 @@ PRIO_TOP_KERNEL = "phx_prio_top_kernel"
 PRIO_ADD_KERNELS = "+".join((PRIO_FILL_KERNEL, PRIO_SPAN_KERNEL, PRIO_TOP_KERNEL))
 PRIO_UPDATE_KERNELS = "+".join((PRIO_ZERO_KERNEL, PRIO_RAISE_KERNEL, PRIO_PATH_KERNEL, PRIO_TOP_KERNEL))
 PRIO_SAMPLE_KERNEL = "phx_prio_sample_kernel"
+FILTER_SUM_KERNEL = "phx_filter_sum_kernel"              # (phx_filter_update: the five names joined by "+")
+FILTER_MEAN_KERNEL = "phx_filter_mean_kernel"
+FILTER_CENTER_KERNEL = "phx_filter_center_kernel"
+FILTER_M2_KERNEL = "phx_filter_m2_kernel"
+FILTER_MERGE_KERNEL = "phx_filter_merge_kernel"
+FILTER_UPDATE_KERNELS = "+".join((FILTER_SUM_KERNEL, FILTER_MEAN_KERNEL, FILTER_CENTER_KERNEL, FILTER_M2_KERNEL, FILTER_MERGE_KERNEL))
+FILTER_APPLY_KERNEL = "phx_filter_apply_kernel"
 MAX_FRAGMENTS = 8
 
 
@@ -384,6 +420,11 @@ assert C.sizeof(PhxPrioAddIO) == 72 and C.sizeof(PhxPrioUpdateIO) == 72 and C.si
 assert [getattr(PhxPrioAddIO, n).offset for n, _ in PhxPrioAddIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
 assert [getattr(PhxPrioUpdateIO, n).offset for n, _ in PhxPrioUpdateIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
 assert [getattr(PhxPrioSampleIO, n).offset for n, _ in PhxPrioSampleIO._fields_] == [0, 8, 16, 24, 32, 40, 48, 56, 64]
+assert C.sizeof(PhxFilterState) == FILTER_STATE_BYTES == 272      # (stated in include/phantom_amd_filter.h, as is every offset below)
+assert [getattr(PhxFilterState, n).offset for n, _ in PhxFilterState._fields_] == [0, 8, 16, 144]
+assert C.sizeof(PhxFilterUpdateIO) == 80 and C.sizeof(PhxFilterApplyIO) == 80
+assert [getattr(PhxFilterUpdateIO, n).offset for n, _ in PhxFilterUpdateIO._fields_] == [0, 4, 8, 16, 20, 24, 32, 40, 48, 56, 64]
+assert [getattr(PhxFilterApplyIO, n).offset for n, _ in PhxFilterApplyIO._fields_] == [0, 4, 8, 16, 20, 24, 32, 40, 48, 56, 64]
 
 _LIB = None
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
@@ -484,11 +525,15 @@ FRAGMENT_OPS = {"phx_gae": PhxGaeIO, "phx_gae_masked": PhxGaeMaskedIO, "phx_vtra
 PRIORITY_OPS = {"phx_prio_add": PhxPrioAddIO, "phx_prio_update": PhxPrioUpdateIO, "phx_prio_sample": PhxPrioSampleIO}
 
 
+# the entry points of include/phantom_amd_filter.h: the same calling convention, a table of their own
+FILTER_OPS = {"phx_filter_update": PhxFilterUpdateIO, "phx_filter_apply": PhxFilterApplyIO}
+
+
 def bind_fragment_ops(lib):
-    """restype / argtypes of the entry points of include/phantom_amd_{gae,vtrace,traj,compact,nstep,episodes,batch,seq,replay,prio}.h:
+    """restype / argtypes of the entry points of include/phantom_amd_{gae,vtrace,traj,compact,nstep,episodes,batch,seq,replay,prio,filter}.h:
     libphantom_amd.so only (the CPU restatement behind phantom_amd.h's symbols has no such functions, so this is not part of
     bind_signatures)"""
-    for entry, io in {**FRAGMENT_OPS, **PRIORITY_OPS}.items():
+    for entry, io in {**FRAGMENT_OPS, **PRIORITY_OPS, **FILTER_OPS}.items():
         getattr(lib, entry).restype = C.c_int32
         getattr(lib, entry).argtypes = [C.POINTER(io), C.c_void_p]
     return lib

@@ -428,7 +428,7 @@ class PhantomEnv:
 
     def sample(self, T: int, actions=None, exo=None, policy=None, explore: bool = False, generator=None, value_fn=None,
                gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0), compact: bool = False,
-               n_step=None, episode_stats=None, batcher=None, replay=None):
+               n_step=None, episode_stats=None, batcher=None, replay=None, obs_filter=None):
         """T steps of every env instance as fused device rollouts, brought to the host ONCE as a ``FragmentBatch``
         (phantom_amd.rollout): agent-major arrays [B, S, T, ..] with the observation each policy acted on (``obs``: what
         ``reset`` or the previous step returned) next to what the step returned (``new_obs``).  The bulk counterpart of the
@@ -516,7 +516,18 @@ class PhantomEnv:
         ids: after the batcher's calls every policy's records are appended to its ring with one ``DeviceEnv.replay_add`` call
         (include/phantom_amd_replay.h), the number of records read on the device where the host does not know it -- no wait, no copy.
         The call returns what it returns without the keyword; ``rb.sample(n)`` then draws a learner's minibatch from everything the
-        ring holds.  ``replay`` without ``batcher``, or with a ``max_seq_len`` batcher: ValueError."""
+        ring holds.  ``replay`` without ``batcher``, or with a ``max_seq_len`` batcher: ValueError.
+
+        ``obs_filter``: a ``phantom_amd.ObsFilter`` of this env (RLlib's ``observation_filter="MeanStdFilter"``).  None: nothing of this
+        runs.  Otherwise, once the fragment's time-major ``obs`` / ``new_obs`` planes exist and before ``value_fn``,
+        ``target_logp_fn`` and every call above reads them, ``obs`` is normalised with ``keep`` = who acted and ``new_obs`` with
+        ``keep`` = ``new_obs_valid`` (``DeviceEnv.filter_apply``, include/phantom_amd_filter.h; rows an agent holds nothing at become
+        +0.0), BOTH with the statistics as they stood when the call began -- the ones a policy with the filter folded in
+        (``ObsFilter.fold``) acted under, so the behaviour policy and the learner see the same normalisation -- and THEN one
+        ``DeviceEnv.filter_update`` folds the raw ``obs`` rows where an agent acted into the statistics.  Apply, then update: the first
+        call with a fresh filter returns the batch it returns without the keyword.  The gathers that follow copy bit for bit, so
+        ``trajectory_new_obs`` and ``nstep_new_obs`` come out normalised; the env's own current observation stays raw.  Works in every
+        mode above."""
         import torch
         from .rollout import FragmentBatch
         if policy is not None and actions is not None:
@@ -607,6 +618,11 @@ class PhantomEnv:
             done += n
             piece_ends.append(done - 1)
         self._episodes_done = ep
+        if obs_filter is not None:                               # apply both planes with the statistics at entry, then fold the raw rows in
+            raw_obs = obs
+            obs = obs_filter.apply(dev, raw_obs, acted)
+            obs_filter.apply(dev, new_obs, nvalid, out=new_obs)
+            obs_filter.update(dev, raw_obs, acted)
         if episode_stats is not None:                            # (on the time-major planes; it does not wait)
             episode_stats.update(dev, rew, trunc, term, acted, rvalid)
         am = lambda x: x.permute(1, 2, 0, *range(3, x.dim())).contiguous()       # [T, B, S, ..] -> [B, S, T, ..] on the device

@@ -1,4 +1,5 @@
-"""FragmentOps: the learner-side entry points over time-major fragments (phx_gae .. phx_replay_sample, phx_prio_*), and their argument checks.
+"""FragmentOps: the learner-side entry points over time-major fragments (phx_gae .. phx_replay_sample, phx_prio_*, phx_filter_*), and their
+argument checks.
 
 None of them needs an env handle: a loaded library and a device are enough, and ``DeviceEnv`` inherits them.  The library
 receives raw device pointers, so every rule a tensor or a scalar has to meet is stated once here, as a helper or as a table the
@@ -89,7 +90,7 @@ class FragmentOps:
             raise DeviceError(f"{what} failed ({rc}): {self._err()}")
 
     def _launch(self, entry, io):
-        """one call of a fragment entry point (``_abi.FRAGMENT_OPS``, ``_abi.PRIORITY_OPS``) on torch's current stream of the device"""
+        """one call of a fragment entry point (``_abi.FRAGMENT_OPS``, ``_abi.PRIORITY_OPS``, ``_abi.FILTER_OPS``) on torch's current stream of the device"""
         torch = _torch()
         with torch.cuda.device(self.device):
             self._check(getattr(self.lib, entry)(C.byref(io), self._stream()), entry)
@@ -633,3 +634,61 @@ class FragmentOps:
         self._launch("phx_prio_sample", _abi.PhxPrioSampleIO(
             capacity=Cn, n=n, seed=seed, draw=draw, ring_state=_ptr(ring_state), tree=_ptr(tree), out_slot=_ptr(oslot), out_priority=_ptr(oprio)))
         return oslot, oprio
+
+    def _filter_planes(self, fn, obs, state, keep, col_class, n_classes):
+        """the arguments ``filter_update`` and ``filter_apply`` share, checked: ``(T, N, D, n_classes)``"""
+        torch = _torch()
+        if obs is None or not hasattr(obs, "dim") or obs.dim() < 3 or not 1 <= obs.shape[-1] <= _abi.FILTER_MAX_DIM:
+            raise ValueError(f"{fn}: `obs` must be a [T, B, S, D] (or [T, N, D]) tensor with 1 <= D <= {_abi.FILTER_MAX_DIM}")
+        shape, T, N = _rows_cols(fn, "`obs` has the leading shape", tuple(obs.shape[:-1]))
+        D = int(obs.shape[-1])
+        n_classes = _int(fn, "n_classes", n_classes, 1, _abi.FILTER_MAX_CLASSES)
+        check_tensor(fn, "obs", obs, torch.float32, shape + (D,), align=16, device=self.device)
+        check_tensor(fn, "state", state, torch.uint8, (n_classes, _abi.FILTER_STATE_BYTES), align=16, device=self.device)
+        self._planes(fn, shape, (("keep", keep, torch.uint8, False),))
+        if col_class is not None:
+            check_tensor(fn, "col_class", col_class, torch.int32, (N,), device=self.device)
+        return T, N, D, n_classes
+
+    def filter_update(self, obs, state, keep=None, col_class=None, n_classes: int = 1, workspace=None):
+        """Fold a time-major fragment's observations into a running mean / M2 per class and feature, on the current stream
+        (phx_filter_update, include/phantom_amd_filter.h): five launches, no atomics, every f64 add in the header's fixed order, so the
+        state is reproducible bit for bit.  ``obs`` is f32 ``[T, B, S, D]`` (or ``[T, N, D]``), D <= 16, 16-byte aligned, on the env's
+        device; ``keep`` u8 of its leading shape (!= 0: the element counts; None: all do); ``col_class`` i32 ``[N]``, every column's
+        class (None: all class 0; a value outside ``[0, n_classes)`` leaves the column out); ``state`` uint8 ``[n_classes, 272]``,
+        records of ``_abi.FILTER_STATE_DTYPE`` (count, updates, mean[16], m2[16]), zero-filled once and 16-byte aligned, updated in
+        place.  A class without a kept element keeps its bytes.  Kept values must be finite.  ``workspace``: f64
+        ``[_abi.filter_workspace_bytes(N, D) // 8]`` scratch, 16-byte aligned; allocated here when None.  The call does not
+        synchronise and returns ``state``."""
+        torch = _torch()
+        T, N, D, n_classes = self._filter_planes("filter_update", obs, state, keep, col_class, n_classes)
+        words = _abi.filter_workspace_bytes(N, D) // 8
+        if workspace is None:
+            workspace = torch.empty((words,), dtype=torch.float64, device=self.device)
+        check_tensor("filter_update", "workspace", workspace, torch.float64, (words,), align=16, device=self.device)
+        self._launch("phx_filter_update", _abi.PhxFilterUpdateIO(
+            T=T, D=D, N=N, n_classes=n_classes, obs=_ptr(obs), keep=_ptr(keep), col_class=_ptr(col_class), state=_ptr(state),
+            workspace=_ptr(workspace)))
+        return state
+
+    def filter_apply(self, obs, state, keep=None, col_class=None, n_classes: int = 1, clip: float = 0.0, out=None):
+        """``out``: a time-major plane normalised with a filter's state as it stands, in ONE launch on the current stream
+        (phx_filter_apply, include/phantom_amd_filter.h).  ``obs`` / ``state`` / ``keep`` / ``col_class`` / ``n_classes`` are
+        ``filter_update``'s; the state is read only.  A kept element of a class's column leaves as ``(x - mean_f) / den_f`` with
+        ``mean_f = (float)mean`` and ``den_f = (float)sqrt(m2 / (count - 1)) + 1e-8f`` (count 1: ``sqrt(mean * mean)``), clamped to
+        ``[-clip, clip]`` when ``clip > 0``; a class that has seen nothing copies its elements bit for bit; every other element is
+        +0.0.  ``out``: f32 of ``obs``'s shape, 16-byte aligned -- ``obs`` itself for in place, any other overlap is refused;
+        allocated here when None.  The call does not synchronise."""
+        torch = _torch()
+        T, N, D, n_classes = self._filter_planes("filter_apply", obs, state, keep, col_class, n_classes)
+        clip32 = float(np.float32(clip)) if isinstance(clip, (int, float, np.floating, np.integer)) and not isinstance(clip, bool) else float("nan")
+        if not clip32 >= 0.0:
+            raise ValueError(f"filter_apply: clip = {clip!r} must be a number >= 0 (0: none)")
+        out, = self._outputs("filter_apply", None if out is None else (out,), ((torch.float32, tuple(obs.shape), REQUIRED),))
+        nbytes = obs.numel() * 4
+        if out.data_ptr() != obs.data_ptr() and out.data_ptr() < obs.data_ptr() + nbytes and obs.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("filter_apply: `out` overlaps `obs` in part (pass `obs` itself for in place)")
+        self._launch("phx_filter_apply", _abi.PhxFilterApplyIO(
+            T=T, D=D, N=N, n_classes=n_classes, clip=clip32, obs=_ptr(obs), keep=_ptr(keep), col_class=_ptr(col_class), state=_ptr(state),
+            out=_ptr(out)))
+        return out

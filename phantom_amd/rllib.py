@@ -410,7 +410,7 @@ class BatchedBaseEnv(_BaseEnvBase):
 
     def sample(self, T: int, actions=None, exo=None, policy_mapping_fn=None, policy=None, explore: bool = False, generator=None,
                value_fn=None, gamma: float = 0.99, lambda_: float = 1.0, target_logp_fn=None, vtrace_clip=(1.0, 1.0, 1.0),
-               compact: bool = False, n_step=None, episode_stats=None, batcher=None, replay=None):
+               compact: bool = False, n_step=None, episode_stats=None, batcher=None, replay=None, obs_filter=None):
         """The bulk exit: T steps of every env instance in fused device rollouts and the fragment as per-policy ``SampleBatch``
         column dicts (phantom_amd.rollout.FragmentBatch.to_sample_batches) -- no python object per (env, agent, step).
         ``actions`` f32 [T, B, S] replays a policy's actions (None: the device's random policy); ``policy`` / ``explore`` /
@@ -428,14 +428,16 @@ class BatchedBaseEnv(_BaseEnvBase):
         with the policy mapping; the call then returns its ``{policy_id: DeviceBatch}`` on the device -- with
         ``TrainBatcher(max_seq_len=L)`` its ``{policy_id: DeviceSeqBatch}`` of padded, shuffled sequences -- and ``policy_mapping_fn``
         here is not used (PhantomEnv.sample).  ``replay``: a ``phantom_amd.ReplayBuffer`` (or a dict of them by policy id) that the
-        batcher's records are appended to on the device (PhantomEnv.sample)."""
+        batcher's records are appended to on the device (PhantomEnv.sample).  ``obs_filter``: a ``phantom_amd.ObsFilter`` whose running
+        mean / std normalise the ``obs`` / ``new_obs`` columns and which the fragment then updates (PhantomEnv.sample)."""
         if batcher is not None or replay is not None:
             return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
                                    lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip, n_step=n_step,
-                                   episode_stats=episode_stats, batcher=batcher, replay=replay)
+                                   episode_stats=episode_stats, batcher=batcher, replay=replay, obs_filter=obs_filter)
         return self.env.sample(T, actions, exo, policy=policy, explore=explore, generator=generator, value_fn=value_fn, gamma=gamma,
                                lambda_=lambda_, target_logp_fn=target_logp_fn, vtrace_clip=vtrace_clip,
-                               compact=compact, n_step=n_step, episode_stats=episode_stats).to_sample_batches(policy_mapping_fn)
+                               compact=compact, n_step=n_step, episode_stats=episode_stats,
+                               obs_filter=obs_filter).to_sample_batches(policy_mapping_fn)
 
     def try_restart(self, env_id: Optional[int] = None) -> None:
         """RLlib calls this after a sub-env fault; the device env has no per-instance process to restart: reset it."""
