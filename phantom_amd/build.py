@@ -13,7 +13,7 @@ LIB = os.path.join(LIB_DIR, "libphantom_amd.so")
 SOURCES = ["phx_api.hip", "phx_spec.hip", "phx_generic.hip", "phx_sc_fused.hip", "phx_sc_rollout.hip", "phx_sc_rollout_sw.hip", "phx_sc_rollout_fsm.hip", "phx_sc_policy.hip", "phx_sc_policy_mfma.hip", "phx_stk_fused.hip",
            "phx_ads_fused.hip", "phx_gae.hip", "phx_gae_masked.hip", "phx_vtrace.hip", "phx_traj_next.hip", "phx_traj_compact.hip", "phx_nstep.hip", "phx_episodes.hip", "phx_train_batch.hip",
            "phx_seq_batch.hip", "phx_replay.hip", "phx_prio.hip", "phx_obs_filter.hip"]
-HEADERS = ["phx_dev.h", "phx_epilogue.h", "phx_launch.h", "phx_spec.h", "phx_sc_policy.h", "phx_generic_sched.hip", os.path.join("..", "..", "include", "phantom_amd.h"),
+HEADERS = ["phx_dev.h", "phx_epilogue.h", "phx_launch.h", "phx_spec.h", "phx_frag.h", "phx_sc_policy.h", "phx_generic_sched.hip", os.path.join("..", "..", "include", "phantom_amd.h"),
            os.path.join("..", "..", "include", "phantom_amd_gae.h"), os.path.join("..", "..", "include", "phantom_amd_vtrace.h"),
            os.path.join("..", "..", "include", "phantom_amd_traj.h"), os.path.join("..", "..", "include", "phantom_amd_compact.h"),
            os.path.join("..", "..", "include", "phantom_amd_nstep.h"), os.path.join("..", "..", "include", "phantom_amd_episodes.h"),

@@ -31,6 +31,7 @@
 
 #include "../../include/phantom_amd_episodes.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int EP_K = 8;            // items per chunk of the scan (tests/test_gpu_episode_stats.py walks T below, at and across it)
 constexpr int EP_LANES = 64;       // output columns per workgroup of the scan: one wave
@@ -212,35 +213,31 @@ static void ep_launch(const int which, const phx_episode_io& io, const int64_t C
 }
 
 extern "C" int phx_episode_stats(const phx_episode_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_episode_stats: null io");
-  if (io->reserved0 != 0) return fail(PHX_EINVAL, "phx_episode_stats: reserved0 must be 0");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_episode_stats: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
+  const char* fn = "phx_episode_stats";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_reserved0(fn, io->reserved0)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
   if (io->G < 1 || io->G > EP_MAX_G) return fail(PHX_EINVAL, "phx_episode_stats: G = %d must lie in [1, %d]", io->G, EP_MAX_G);
   if (io->N % io->G != 0) return fail(PHX_EINVAL, "phx_episode_stats: N = %lld must be a multiple of G = %d", (long long)io->N, io->G);
   const int64_t C = io->N / io->G;
   if (io->K < 1 || C % io->K != 0)
     return fail(PHX_EINVAL, "phx_episode_stats: K = %d must be >= 1 and divide the %lld output columns", io->K, (long long)C);
-  if (C > (int64_t)EP_LANES * 0x7fffffff)
-    return fail(PHX_EINVAL, "phx_episode_stats: %lld output columns are beyond one launch's grid", (long long)C);
-  if (!io->reward || !io->truncated || !io->col_stats) return fail(PHX_EINVAL, "phx_episode_stats: reward, truncated and col_stats are required");
+  if (C > (int64_t)EP_LANES * 0x7fffffff) return frag_beyond_grid(fn, "%lld output columns are", (long long)C);
+  if (const int rc = frag_required(fn, io->reward && io->truncated && io->col_stats, "reward, truncated and col_stats")) return rc;
   if ((io->carry_return == nullptr) != (io->carry_len == nullptr))
     return fail(PHX_EINVAL, "phx_episode_stats: carry_return and carry_len come together");
-  if (((uintptr_t)io->reward | (uintptr_t)io->carry_return | (uintptr_t)io->carry_len) & 3u)
-    return fail(PHX_EINVAL, "phx_episode_stats: reward, carry_return and carry_len must be 4-byte aligned");
-  if (((uintptr_t)io->episode_return | (uintptr_t)io->episode_len | (uintptr_t)io->col_stats | (uintptr_t)io->summary) & 15u)
-    return fail(PHX_EINVAL, "phx_episode_stats: episode_return, episode_len, col_stats and summary must be 16-byte aligned");
+  if (const int rc = frag_aligned(fn, frag_bits(io->reward, io->carry_return, io->carry_len), 4, "reward, carry_return and carry_len")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->episode_return, io->episode_len, io->col_stats, io->summary), 16,
+                                  "episode_return, episode_len, col_stats and summary"))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
   const int which = (io->G > 1 ? 8 : 0) | (io->terminated ? 4 : 0) | (io->acted ? 2 : 0) | (io->reward_valid ? 1 : 0);
   ep_launch<15>(which, *io, C, st);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_episode_stats: the scan: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_episode_scan_kernel");
+  if (const int rc = call.launched("the scan", "phx_episode_scan_kernel")) return rc;
   if (io->summary) {
     hipLaunchKernelGGL(phx_episode_reduce_kernel, dim3((unsigned)io->K), dim3(EP_RED), 0, st, *io, C / io->K);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_episode_stats: the reduction: %s", hipGetErrorString(he));
-    phx_note_kernel("phx_episode_reduce_kernel");
+    if (const int rc = call.launched("the reduction", "phx_episode_reduce_kernel")) return rc;
   }
   return PHX_OK;
 }

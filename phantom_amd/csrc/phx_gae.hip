@@ -18,6 +18,7 @@
 
 #include "../../include/phantom_amd_gae.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int GAE_K = 16;          // rows per chunk (tests/test_gpu_gae.py walks T below, at and across it)
 constexpr int GAE_LANES = 64;      // columns per workgroup: one wave
@@ -93,17 +94,15 @@ static void gae_launch(const phx_gae_io& io, const float gl, hipStream_t st) {
 }
 
 extern "C" int phx_gae(const phx_gae_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_gae: null io");
-  if (io->reserved0 != 0) return fail(PHX_EINVAL, "phx_gae: reserved0 must be 0");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_gae: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)GAE_LANES * 0x7fffffff) return fail(PHX_EINVAL, "phx_gae: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (!(io->gamma >= 0.0f && io->gamma <= 1.0f) || !(io->lambda >= 0.0f && io->lambda <= 1.0f))
-    return fail(PHX_EINVAL, "phx_gae: gamma = %g and lambda = %g must lie in [0, 1]", (double)io->gamma, (double)io->lambda);
-  if (!io->reward || !io->truncated || !io->advantage) return fail(PHX_EINVAL, "phx_gae: reward, truncated and advantage are required");
-  if (((uintptr_t)io->reward | (uintptr_t)io->vf_pred | (uintptr_t)io->vf_next) & 3u)
-    return fail(PHX_EINVAL, "phx_gae: reward, vf_pred and vf_next must be 4-byte aligned");
-  if (((uintptr_t)io->advantage | (uintptr_t)io->value_target) & 15u)
-    return fail(PHX_EINVAL, "phx_gae: advantage and value_target must be 16-byte aligned");
+  const char* fn = "phx_gae";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_reserved0(fn, io->reserved0)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, GAE_LANES)) return rc;
+  if (const int rc = frag_gamma_lambda(fn, io->gamma, io->lambda)) return rc;
+  if (const int rc = frag_required(fn, io->reward && io->truncated && io->advantage, "reward, truncated and advantage")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->reward, io->vf_pred, io->vf_next), 4, "reward, vf_pred and vf_next")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->advantage, io->value_target), 16, "advantage and value_target")) return rc;
   const float gl = io->gamma * io->lambda;               // one f32 multiply (the build has -ffp-contract=off)
   const hipStream_t st = (hipStream_t)stream;
   const int which = (io->vf_pred ? 4 : 0) | (io->vf_next ? 2 : 0) | (io->terminated ? 1 : 0);
@@ -117,9 +116,5 @@ extern "C" int phx_gae(const phx_gae_io* io, void* stream) {
     case 6: gae_launch<true, true, false>(*io, gl, st); break;
     default: gae_launch<true, true, true>(*io, gl, st); break;
   }
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_gae: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_gae_kernel");
-  return PHX_OK;
+  return FragCall{fn}.launched(nullptr, "phx_gae_kernel");
 }

@@ -20,6 +20,7 @@
 
 #include "../../include/phantom_amd_gae.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int GMK_K = 16;          // rows per chunk (tests/test_gpu_gae_masked.py walks T below, at and across it)
 constexpr int GMK_LANES = 64;      // columns per workgroup: one wave
@@ -123,25 +124,18 @@ static void gmk_launch(const int which, const phx_gae_masked_io& io, const float
 }
 
 extern "C" int phx_gae_masked(const phx_gae_masked_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_gae_masked: null io");
-  if (io->reserved0 != 0) return fail(PHX_EINVAL, "phx_gae_masked: reserved0 must be 0");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_gae_masked: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)GMK_LANES * 0x7fffffff)
-    return fail(PHX_EINVAL, "phx_gae_masked: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (!(io->gamma >= 0.0f && io->gamma <= 1.0f) || !(io->lambda >= 0.0f && io->lambda <= 1.0f))
-    return fail(PHX_EINVAL, "phx_gae_masked: gamma = %g and lambda = %g must lie in [0, 1]", (double)io->gamma, (double)io->lambda);
-  if (!io->reward || !io->truncated || !io->advantage)
-    return fail(PHX_EINVAL, "phx_gae_masked: reward, truncated and advantage are required");
-  if (((uintptr_t)io->reward | (uintptr_t)io->vf_pred | (uintptr_t)io->vf_next) & 3u)
-    return fail(PHX_EINVAL, "phx_gae_masked: reward, vf_pred and vf_next must be 4-byte aligned");
-  if (((uintptr_t)io->advantage | (uintptr_t)io->value_target | (uintptr_t)io->reward_sum) & 15u)
-    return fail(PHX_EINVAL, "phx_gae_masked: advantage, value_target and reward_sum must be 16-byte aligned");
+  const char* fn = "phx_gae_masked";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_reserved0(fn, io->reserved0)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, GMK_LANES)) return rc;
+  if (const int rc = frag_gamma_lambda(fn, io->gamma, io->lambda)) return rc;
+  if (const int rc = frag_required(fn, io->reward && io->truncated && io->advantage, "reward, truncated and advantage")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->reward, io->vf_pred, io->vf_next), 4, "reward, vf_pred and vf_next")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->advantage, io->value_target, io->reward_sum), 16, "advantage, value_target and reward_sum"))
+    return rc;
   const float gl = io->gamma * io->lambda;               // one f32 multiply (the build has -ffp-contract=off)
   const int which = (io->vf_pred ? 16 : 0) | (io->vf_next ? 8 : 0) | (io->terminated ? 4 : 0) | (io->acted ? 2 : 0) | (io->reward_valid ? 1 : 0);
   gmk_launch<31>(which, *io, gl, (hipStream_t)stream);
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_gae_masked: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_gae_masked_kernel");
-  return PHX_OK;
+  return FragCall{fn}.launched(nullptr, "phx_gae_masked_kernel");
 }

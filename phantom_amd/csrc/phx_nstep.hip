@@ -34,6 +34,7 @@
 
 #include "../../include/phantom_amd_nstep.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int NS_K = 16;           // rows per chunk of the succ scan (tests/test_gpu_nstep.py walks T below, at and across it)
 constexpr int NS_LANES = 64;       // columns per workgroup of the succ scan: one wave
@@ -195,48 +196,40 @@ static void ng_launch(const phx_nstep_io& io, hipStream_t st) {
 }
 
 extern "C" int phx_nstep(const phx_nstep_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_nstep: null io");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_nstep: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)NS_LANES * 0x7fffffff) return fail(PHX_EINVAL, "phx_nstep: N = %lld is beyond one launch's grid", (long long)io->N);
+  const char* fn = "phx_nstep";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, NS_LANES)) return rc;
   if (io->n < 1 || io->n > NSTEP_MAX_N) return fail(PHX_EINVAL, "phx_nstep: n = %d must lie in [1, %d]", io->n, NSTEP_MAX_N);
-  if (!(io->gamma >= 0.0f && io->gamma <= 1.0f)) return fail(PHX_EINVAL, "phx_nstep: gamma = %g must lie in [0, 1]", (double)io->gamma);
-  if (!io->reward || !io->truncated) return fail(PHX_EINVAL, "phx_nstep: reward and truncated are required");
-  if (!io->nstep_reward || !io->nstep_discount || !io->nstep_last || !io->nstep_terminated || !io->nstep_truncated || !io->nstep_next_row)
-    return fail(PHX_EINVAL, "phx_nstep: nstep_reward, nstep_discount, nstep_last, nstep_terminated, nstep_truncated and nstep_next_row are required");
+  if (!frag_unit(io->gamma)) return fail(PHX_EINVAL, "phx_nstep: gamma = %g must lie in [0, 1]", (double)io->gamma);
+  if (const int rc = frag_required(fn, io->reward && io->truncated, "reward and truncated")) return rc;
+  if (const int rc = frag_required(fn, io->nstep_reward && io->nstep_discount && io->nstep_last && io->nstep_terminated && io->nstep_truncated &&
+                                           io->nstep_next_row,
+                                   "nstep_reward, nstep_discount, nstep_last, nstep_terminated, nstep_truncated and nstep_next_row"))
+    return rc;
   if (io->acted && !io->succ_row) return fail(PHX_EINVAL, "phx_nstep: acted needs succ_row");
   if (io->nstep_next_obs) {
     if (!io->next_obs) return fail(PHX_EINVAL, "phx_nstep: nstep_next_obs needs next_obs");
     if (io->D < 1 || io->D > 64) return fail(PHX_EINVAL, "phx_nstep: D = %d must lie in [1, 64] when nstep_next_obs is given", io->D);
-    if (io->N * io->D > (int64_t)NG_THREADS * 0x7fffffff)
-      return fail(PHX_EINVAL, "phx_nstep: N = %lld with D = %d is beyond one launch's grid", (long long)io->N, io->D);
+    if (io->N * io->D > (int64_t)NG_THREADS * 0x7fffffff) return frag_beyond_grid(fn, "N = %lld with D = %d is", (long long)io->N, io->D);
   }
-  if (((uintptr_t)io->reward | (uintptr_t)io->next_row | (uintptr_t)io->next_obs) & 3u)
-    return fail(PHX_EINVAL, "phx_nstep: reward, next_row and next_obs must be 4-byte aligned");
-  if (((uintptr_t)io->succ_row | (uintptr_t)io->nstep_reward | (uintptr_t)io->nstep_discount | (uintptr_t)io->nstep_last |
-       (uintptr_t)io->nstep_terminated | (uintptr_t)io->nstep_truncated | (uintptr_t)io->nstep_next_row | (uintptr_t)io->nstep_next_obs) & 15u)
-    return fail(PHX_EINVAL, "phx_nstep: succ_row and the nstep_ outputs must be 16-byte aligned");
+  if (const int rc = frag_aligned(fn, frag_bits(io->reward, io->next_row, io->next_obs), 4, "reward, next_row and next_obs")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->succ_row, io->nstep_reward, io->nstep_discount, io->nstep_last, io->nstep_terminated,
+                                                io->nstep_truncated, io->nstep_next_row, io->nstep_next_obs),
+                                  16, "succ_row and the nstep_ outputs"))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
-  hipError_t he;
-  bool noted = false;
+  FragCall call{fn};
   if (io->acted) {
     hipLaunchKernelGGL(phx_nstep_succ_kernel, dim3((unsigned)((io->N + NS_LANES - 1) / NS_LANES)), dim3(NS_LANES), 0, st, *io);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_nstep: the successor scan: %s", hipGetErrorString(he));
-    phx_note_reset();
-    phx_note_kernel("phx_nstep_succ_kernel");
-    noted = true;
+    if (const int rc = call.launched("the successor scan", "phx_nstep_succ_kernel")) return rc;
   }
   const int which = (io->terminated ? 4 : 0) | (io->acted ? 2 : 0) | (io->next_row ? 1 : 0);
   nf_launch<7>(which, *io, st);
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_nstep: the fold: %s", hipGetErrorString(he));
-  if (!noted) phx_note_reset();
-  phx_note_kernel("phx_nstep_fold_kernel");
+  if (const int rc = call.launched("the fold", "phx_nstep_fold_kernel")) return rc;
   if (io->nstep_next_obs) {
     if (io->N * io->D <= 0xffffff00LL) ng_launch<uint32_t>(*io, st); else ng_launch<uint64_t>(*io, st);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_nstep: the gather: %s", hipGetErrorString(he));
-    phx_note_kernel("phx_nstep_gather_kernel");
+    if (const int rc = call.launched("the gather", "phx_nstep_gather_kernel")) return rc;
   }
   return PHX_OK;
 }

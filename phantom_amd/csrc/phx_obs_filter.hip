@@ -29,6 +29,7 @@
 
 #include "../../include/phantom_amd_filter.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int FL_LANES = 64;         // columns per workgroup of the two column walks: one wave
 constexpr int FL_RED = 256;          // the folds' workgroup: the header's 256 lane values
@@ -341,75 +342,51 @@ static void fa_launch(const phx_filter_apply_io& io, const int64_t E, hipStream_
 // the checks the two calls share; `fn` names the call in the message
 static int fl_check(const char* fn, const int T, const int D, const int64_t N, const int n_classes, const void* obs, const void* col_class,
                     const void* state) {
-  if (T < 1 || N < 1) return fail(PHX_EINVAL, "%s: T = %d and N = %lld must be >= 1", fn, T, (long long)N);
+  if (const int rc = frag_rows_cols(fn, T, N)) return rc;
   if (D < 1 || D > FL_MD) return fail(PHX_EINVAL, "%s: D = %d must lie in [1, %d]", fn, D, FL_MD);
   if (n_classes < 1 || n_classes > FL_MC) return fail(PHX_EINVAL, "%s: n_classes = %d must lie in [1, %d]", fn, n_classes, FL_MC);
-  if (!obs || !state) return fail(PHX_EINVAL, "%s: obs and state are required", fn);
-  if (((uintptr_t)obs | (uintptr_t)state) & 15u) return fail(PHX_EINVAL, "%s: obs and state must be 16-byte aligned", fn);
-  if ((uintptr_t)col_class & 3u) return fail(PHX_EINVAL, "%s: col_class must be 4-byte aligned", fn);
-  return PHX_OK;
+  if (const int rc = frag_required(fn, obs && state, "obs and state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(obs, state), 16, "obs and state")) return rc;
+  return frag_aligned(fn, frag_bits(col_class), 4, "col_class");
 }
 
 extern "C" int phx_filter_update(const phx_filter_update_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_filter_update: null io");
-  if (io->reserved0 != 0 || io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_filter_update: the reserved fields must be 0");
-  if (const int rc = fl_check("phx_filter_update", io->T, io->D, io->N, io->n_classes, io->obs, io->col_class, io->state)) return rc;
+  const char* fn = "phx_filter_update";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved, io->reserved0, "the reserved fields")) return rc;
+  if (const int rc = fl_check(fn, io->T, io->D, io->N, io->n_classes, io->obs, io->col_class, io->state)) return rc;
   if (!io->workspace || ((uintptr_t)io->workspace & 15u))
     return fail(PHX_EINVAL, "phx_filter_update: workspace is required and must be 16-byte aligned");
-  if (io->N > (int64_t)FL_LANES * 0x7fffffff)
-    return fail(PHX_EINVAL, "phx_filter_update: %lld columns are beyond one launch's grid", (long long)io->N);
+  if (io->N > (int64_t)FL_LANES * 0x7fffffff) return frag_beyond_grid(fn, "%lld columns are", (long long)io->N);
   const hipStream_t st = (hipStream_t)stream;
   const unsigned folds = (unsigned)(io->n_classes * io->D);
-  const char* what = "the sum";
-  phx_note_reset();
+  FragCall call{fn};
   fl_launch_walk<FL_MD>(*io, false, st);
-  hipError_t he = hipGetLastError();
-  if (he == hipSuccess) {
-    phx_note_kernel("phx_filter_sum_kernel");
-    what = "the mean";
-    hipLaunchKernelGGL(phx_filter_mean_kernel, dim3(folds), dim3(FL_RED), 0, st, *io);
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) {
-    phx_note_kernel("phx_filter_mean_kernel");
-    what = "the centred pass";
-    fl_launch_walk<FL_MD>(*io, true, st);
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) {
-    phx_note_kernel("phx_filter_center_kernel");
-    what = "the M2 fold";
-    hipLaunchKernelGGL(phx_filter_m2_kernel, dim3(folds), dim3(FL_RED), 0, st, *io);
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) {
-    phx_note_kernel("phx_filter_m2_kernel");
-    what = "the merge";
-    hipLaunchKernelGGL(phx_filter_merge_kernel, dim3(1), dim3(FL_MC * FL_MD), 0, st, *io);
-    he = hipGetLastError();
-  }
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_filter_update: %s: %s", what, hipGetErrorString(he));
-  phx_note_kernel("phx_filter_merge_kernel");
-  return PHX_OK;
+  if (const int rc = call.launched("the sum", "phx_filter_sum_kernel")) return rc;
+  hipLaunchKernelGGL(phx_filter_mean_kernel, dim3(folds), dim3(FL_RED), 0, st, *io);
+  if (const int rc = call.launched("the mean", "phx_filter_mean_kernel")) return rc;
+  fl_launch_walk<FL_MD>(*io, true, st);
+  if (const int rc = call.launched("the centred pass", "phx_filter_center_kernel")) return rc;
+  hipLaunchKernelGGL(phx_filter_m2_kernel, dim3(folds), dim3(FL_RED), 0, st, *io);
+  if (const int rc = call.launched("the M2 fold", "phx_filter_m2_kernel")) return rc;
+  hipLaunchKernelGGL(phx_filter_merge_kernel, dim3(1), dim3(FL_MC * FL_MD), 0, st, *io);
+  return call.launched("the merge", "phx_filter_merge_kernel");
 }
 
 extern "C" int phx_filter_apply(const phx_filter_apply_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_filter_apply: null io");
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_filter_apply: the reserved fields must be 0");
-  if (const int rc = fl_check("phx_filter_apply", io->T, io->D, io->N, io->n_classes, io->obs, io->col_class, io->state)) return rc;
+  const char* fn = "phx_filter_apply";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved, 0, "the reserved fields")) return rc;
+  if (const int rc = fl_check(fn, io->T, io->D, io->N, io->n_classes, io->obs, io->col_class, io->state)) return rc;
   if (!io->out || ((uintptr_t)io->out & 15u)) return fail(PHX_EINVAL, "phx_filter_apply: out is required and must be 16-byte aligned");
   if (!(io->clip >= 0.0f)) return fail(PHX_EINVAL, "phx_filter_apply: clip = %g must be >= 0 (0: none)", (double)io->clip);
   // one row's floats and a workgroup's chunk in 32 bits, the chunks in one grid
   if (io->N > (0x7fffffffLL - FA_CHUNK) / io->D || (int64_t)io->T > (0x7fffffffLL * FA_CHUNK) / (io->N * io->D))
-    return fail(PHX_EINVAL, "phx_filter_apply: T = %d rows of N = %lld columns are beyond one launch's grid", io->T, (long long)io->N);
+    return frag_beyond_grid(fn, "T = %d rows of N = %lld columns are", io->T, (long long)io->N);
   const int64_t E = (int64_t)io->T * io->N * io->D;
   const uintptr_t a = (uintptr_t)io->obs, b = (uintptr_t)io->out, bytes = (uintptr_t)E * 4u;
   if (a != b && a < b + bytes && b < a + bytes)
     return fail(PHX_EINVAL, "phx_filter_apply: out overlaps obs in part (out == obs, exactly in place, is allowed)");
   fa_launch<FL_MD>(*io, E, (hipStream_t)stream);
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_filter_apply: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_filter_apply_kernel");
-  return PHX_OK;
+  return FragCall{fn}.launched(nullptr, "phx_filter_apply_kernel");
 }

@@ -25,6 +25,7 @@
 
 #include "../../include/phantom_amd_prio.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int PR_THREADS = 256;      // a workgroup: four waves
 constexpr int PR_LEVELS = 9;         // levels 0 .. L, L <= 8 for C <= 2^30
@@ -262,91 +263,85 @@ static PrLevel pr_level(const PrLayout& ly, const int l) {
 
 static unsigned pr_blocks(const int64_t threads) { return (unsigned)(threads < 1 ? 1 : (threads + PR_THREADS - 1) / PR_THREADS); }
 
-static int pr_launched(const char* fn, const char* what, const char* kernel) {
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "%s: %s: %s", fn, what, hipGetErrorString(he));
-  phx_note_kernel(kernel);
+static int pr_top(FragCall& call, float* tree, const PrLayout& ly, const hipStream_t st) {
+  hipLaunchKernelGGL(phx_prio_top_kernel, dim3(1), dim3(PR_THREADS), 0, st, tree, ly);
+  return call.launched("the top levels", "phx_prio_top_kernel");
+}
+
+// the three calls' capacity rule
+static int pr_capacity(const char* fn, const int64_t capacity) {
+  if (capacity < 1 || capacity > PHX_PRIO_MAX_CAPACITY) return fail(PHX_EINVAL, "%s: capacity = %lld must lie in [1, 2^30]", fn, (long long)capacity);
   return PHX_OK;
 }
 
-static int pr_top(const char* fn, float* tree, const PrLayout& ly, const hipStream_t st) {
-  hipLaunchKernelGGL(phx_prio_top_kernel, dim3(1), dim3(PR_THREADS), 0, st, tree, ly);
-  return pr_launched(fn, "the top levels", "phx_prio_top_kernel");
-}
-
 extern "C" int phx_prio_add(const phx_prio_add_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_prio_add: null io");
-  if (io->capacity < 1 || io->capacity > PHX_PRIO_MAX_CAPACITY)
-    return fail(PHX_EINVAL, "phx_prio_add: capacity = %lld must lie in [1, 2^30]", (long long)io->capacity);
-  if (io->src_capacity < 0) return fail(PHX_EINVAL, "phx_prio_add: src_capacity = %lld must be >= 0", (long long)io->src_capacity);
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_prio_add: reserved must be 0");
-  if (!io->count_ptr && (io->count < 0 || io->count > io->src_capacity))
-    return fail(PHX_EINVAL, "phx_prio_add: count = %lld must lie in [0, src_capacity = %lld]", (long long)io->count, (long long)io->src_capacity);
-  if (!io->ring_state || !io->tree || !io->state) return fail(PHX_EINVAL, "phx_prio_add: ring_state, tree and state are required");
-  if (((uintptr_t)io->tree | (uintptr_t)io->state) & 15u) return fail(PHX_EINVAL, "phx_prio_add: tree and state must be 16-byte aligned");
-  if (((uintptr_t)io->count_ptr | (uintptr_t)io->ring_state) & 7u)
-    return fail(PHX_EINVAL, "phx_prio_add: count_ptr and ring_state must be 8-byte aligned");
+  const char* fn = "phx_prio_add";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = pr_capacity(fn, io->capacity)) return rc;
+  if (const int rc = frag_at_least(fn, "src_capacity", io->src_capacity, 0)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved)) return rc;
+  if (const int rc = frag_count(fn, io->count_ptr, io->count, io->src_capacity)) return rc;
+  if (const int rc = frag_required(fn, io->ring_state && io->tree && io->state, "ring_state, tree and state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->tree, io->state), 16, "tree and state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->count_ptr, io->ring_state), 8, "count_ptr and ring_state")) return rc;
   const int64_t C = io->capacity;
   const int64_t most = io->src_capacity < C ? io->src_capacity : C;        // the host does not know K: the grids are sized from this
   const PrLayout ly = pr_layout(C);
   const hipStream_t st = (hipStream_t)stream;
-  phx_note_reset();
+  FragCall call{fn};
   hipLaunchKernelGGL(phx_prio_fill_kernel, dim3(pr_blocks(most)), dim3(PR_THREADS), 0, st, io->tree, io->state, io->ring_state, io->count_ptr,
                      io->count, io->src_capacity, C);
-  int rc = pr_launched("phx_prio_add", "the fill", "phx_prio_fill_kernel");
-  for (int l = 1; rc == PHX_OK && l < ly.top; ++l) {                       // two runs of `most` slots in all: at most most / 16^l + 3 nodes
+  if (const int rc = call.launched("the fill", "phx_prio_fill_kernel")) return rc;
+  for (int l = 1; l < ly.top; ++l) {                                       // two runs of `most` slots in all: at most most / 16^l + 3 nodes
     hipLaunchKernelGGL(phx_prio_span_kernel, dim3(pr_blocks((most >> (4 * l)) + 3)), dim3(PR_THREADS), 0, st, io->tree, io->ring_state,
                        io->count_ptr, io->count, io->src_capacity, C, pr_level(ly, l));
-    rc = pr_launched("phx_prio_add", "a sparse level", "phx_prio_span_kernel");
+    if (const int rc = call.launched("a sparse level", "phx_prio_span_kernel")) return rc;
   }
-  return rc == PHX_OK ? pr_top("phx_prio_add", io->tree, ly, st) : rc;
+  return pr_top(call, io->tree, ly, st);
 }
 
 extern "C" int phx_prio_update(const phx_prio_update_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_prio_update: null io");
-  if (io->capacity < 1 || io->capacity > PHX_PRIO_MAX_CAPACITY)
-    return fail(PHX_EINVAL, "phx_prio_update: capacity = %lld must lie in [1, 2^30]", (long long)io->capacity);
-  if (io->n < 1) return fail(PHX_EINVAL, "phx_prio_update: n = %lld must be >= 1", (long long)io->n);
-  if (io->n > (int64_t)PR_THREADS * 0x7fffffffLL) return fail(PHX_EINVAL, "phx_prio_update: n = %lld is beyond one launch's grid", (long long)io->n);
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_prio_update: reserved must be 0");
-  if (!io->slot_in || !io->priority || !io->ring_state || !io->tree || !io->state)
-    return fail(PHX_EINVAL, "phx_prio_update: slot_in, priority, ring_state, tree and state are required");
-  if (((uintptr_t)io->tree | (uintptr_t)io->state) & 15u) return fail(PHX_EINVAL, "phx_prio_update: tree and state must be 16-byte aligned");
-  if (((uintptr_t)io->slot_in | (uintptr_t)io->ring_state) & 7u)
-    return fail(PHX_EINVAL, "phx_prio_update: slot_in and ring_state must be 8-byte aligned");
-  if ((uintptr_t)io->priority & 3u) return fail(PHX_EINVAL, "phx_prio_update: priority must be 4-byte aligned");
+  const char* fn = "phx_prio_update";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = pr_capacity(fn, io->capacity)) return rc;
+  if (const int rc = frag_at_least(fn, "n", io->n, 1)) return rc;
+  if (const int rc = frag_one_grid(fn, "n", io->n, PR_THREADS)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved)) return rc;
+  if (const int rc = frag_required(fn, io->slot_in && io->priority && io->ring_state && io->tree && io->state,
+                                   "slot_in, priority, ring_state, tree and state"))
+    return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->tree, io->state), 16, "tree and state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->slot_in, io->ring_state), 8, "slot_in and ring_state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->priority), 4, "priority")) return rc;
   const int64_t C = io->capacity;
   const PrLayout ly = pr_layout(C);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid(pr_blocks(io->n)), block(PR_THREADS);
-  phx_note_reset();
+  FragCall call{fn};
   hipLaunchKernelGGL(phx_prio_zero_kernel, grid, block, 0, st, io->tree, io->ring_state, io->slot_in, io->n, C);
-  int rc = pr_launched("phx_prio_update", "the zero fill", "phx_prio_zero_kernel");
-  if (rc != PHX_OK) return rc;
+  if (const int rc = call.launched("the zero fill", "phx_prio_zero_kernel")) return rc;
   hipLaunchKernelGGL(phx_prio_raise_kernel, grid, block, 0, st, io->tree, io->state, io->ring_state, io->slot_in, io->priority, io->n, C);
-  rc = pr_launched("phx_prio_update", "the raise", "phx_prio_raise_kernel");
-  for (int l = 1; rc == PHX_OK && l < ly.top; ++l) {
+  if (const int rc = call.launched("the raise", "phx_prio_raise_kernel")) return rc;
+  for (int l = 1; l < ly.top; ++l) {
     hipLaunchKernelGGL(phx_prio_path_kernel, grid, block, 0, st, io->tree, io->ring_state, io->slot_in, io->n, C, pr_level(ly, l));
-    rc = pr_launched("phx_prio_update", "a sparse level", "phx_prio_path_kernel");
+    if (const int rc = call.launched("a sparse level", "phx_prio_path_kernel")) return rc;
   }
-  return rc == PHX_OK ? pr_top("phx_prio_update", io->tree, ly, st) : rc;
+  return pr_top(call, io->tree, ly, st);
 }
 
 extern "C" int phx_prio_sample(const phx_prio_sample_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_prio_sample: null io");
-  if (io->capacity < 1 || io->capacity > PHX_PRIO_MAX_CAPACITY)
-    return fail(PHX_EINVAL, "phx_prio_sample: capacity = %lld must lie in [1, 2^30]", (long long)io->capacity);
-  if (io->n < 1) return fail(PHX_EINVAL, "phx_prio_sample: n = %lld must be >= 1", (long long)io->n);
-  if (io->n > (int64_t)PR_THREADS * 0x7fffffffLL) return fail(PHX_EINVAL, "phx_prio_sample: n = %lld is beyond one launch's grid", (long long)io->n);
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_prio_sample: reserved must be 0");
-  if (!io->ring_state || !io->tree || !io->out_slot || !io->out_priority)
-    return fail(PHX_EINVAL, "phx_prio_sample: ring_state, tree, out_slot and out_priority are required");
-  if (((uintptr_t)io->tree | (uintptr_t)io->out_slot | (uintptr_t)io->out_priority) & 15u)
-    return fail(PHX_EINVAL, "phx_prio_sample: tree, out_slot and out_priority must be 16-byte aligned");
-  if ((uintptr_t)io->ring_state & 7u) return fail(PHX_EINVAL, "phx_prio_sample: ring_state must be 8-byte aligned");
+  const char* fn = "phx_prio_sample";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = pr_capacity(fn, io->capacity)) return rc;
+  if (const int rc = frag_at_least(fn, "n", io->n, 1)) return rc;
+  if (const int rc = frag_one_grid(fn, "n", io->n, PR_THREADS)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved)) return rc;
+  if (const int rc = frag_required(fn, io->ring_state && io->tree && io->out_slot && io->out_priority, "ring_state, tree, out_slot and out_priority"))
+    return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->tree, io->out_slot, io->out_priority), 16, "tree, out_slot and out_priority")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->ring_state), 8, "ring_state")) return rc;
   const uint64_t s0 = pr_mix(pr_mix(io->seed + 0x9E3779B97F4A7C15ull) ^ io->draw);
-  phx_note_reset();
   hipLaunchKernelGGL(phx_prio_sample_kernel, dim3(pr_blocks(io->n)), dim3(PR_THREADS), 0, (hipStream_t)stream, io->tree, io->ring_state,
                      io->out_slot, io->out_priority, io->n, io->capacity, s0, pr_layout(io->capacity));
-  return pr_launched("phx_prio_sample", "the draw", "phx_prio_sample_kernel");
+  return FragCall{fn}.launched("the draw", "phx_prio_sample_kernel");
 }

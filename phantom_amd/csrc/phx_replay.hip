@@ -22,6 +22,7 @@
 
 #include "../../include/phantom_amd_replay.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int RP_THREADS = 256;      // a workgroup: four waves
 constexpr int RP_U = 4;              // pieces per lane and tile: loads in flight per lane
@@ -155,64 +156,48 @@ static RpShape rp_shape(const int row_words) {
   return sh;
 }
 
-// the tiles of `records` records, or -1 beyond one launch's grid
-static int64_t rp_tiles(const int64_t records, const RpShape& sh) {
-  const int64_t tiles = records / sh.R + (records % sh.R ? 1 : 0);
-  return tiles > 0x7fffffffLL ? -1 : tiles;
-}
+// the tiles of `records` records (sh.R a tile: what frag_one_grid is given)
+static int64_t rp_tiles(const int64_t records, const RpShape& sh) { return records / sh.R + (records % sh.R ? 1 : 0); }
 
 extern "C" int phx_replay_add(const phx_replay_add_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_replay_add: null io");
-  if (io->capacity < 1) return fail(PHX_EINVAL, "phx_replay_add: capacity = %lld must be >= 1", (long long)io->capacity);
-  if (io->src_capacity < 0) return fail(PHX_EINVAL, "phx_replay_add: src_capacity = %lld must be >= 0", (long long)io->src_capacity);
-  if (io->row_words < 4 || io->row_words > 256 || (io->row_words & 3))
-    return fail(PHX_EINVAL, "phx_replay_add: row_words = %d must be a multiple of 4 in [4, 256]", io->row_words);
-  if (io->reserved0 != 0 || io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_replay_add: reserved must be 0");
-  if (!io->count_ptr && (io->count < 0 || io->count > io->src_capacity))
-    return fail(PHX_EINVAL, "phx_replay_add: count = %lld must lie in [0, src_capacity = %lld]", (long long)io->count, (long long)io->src_capacity);
-  if (!io->ring || !io->state) return fail(PHX_EINVAL, "phx_replay_add: ring and state are required");
+  const char* fn = "phx_replay_add";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_at_least(fn, "capacity", io->capacity, 1)) return rc;
+  if (const int rc = frag_at_least(fn, "src_capacity", io->src_capacity, 0)) return rc;
+  if (const int rc = frag_row_words(fn, io->row_words)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved, io->reserved0)) return rc;
+  if (const int rc = frag_count(fn, io->count_ptr, io->count, io->src_capacity)) return rc;
+  if (const int rc = frag_required(fn, io->ring && io->state, "ring and state")) return rc;
   if (io->src_capacity > 0 && !io->src) return fail(PHX_EINVAL, "phx_replay_add: src is required with src_capacity > 0");
-  if (((uintptr_t)io->src | (uintptr_t)io->ring | (uintptr_t)io->state) & 15u)
-    return fail(PHX_EINVAL, "phx_replay_add: src, ring and state must be 16-byte aligned");
-  if ((uintptr_t)io->count_ptr & 7u) return fail(PHX_EINVAL, "phx_replay_add: count_ptr must be 8-byte aligned");
+  if (const int rc = frag_aligned(fn, frag_bits(io->src, io->ring, io->state), 16, "src, ring and state")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->count_ptr), 8, "count_ptr")) return rc;
   const RpShape sh = rp_shape(io->row_words);
+  if (const int rc = frag_one_grid(fn, "src_capacity", io->src_capacity, sh.R)) return rc;
   const int64_t tiles = rp_tiles(io->src_capacity, sh);
-  if (tiles < 0) return fail(PHX_EINVAL, "phx_replay_add: src_capacity = %lld is beyond one launch's grid", (long long)io->src_capacity);
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
   const unsigned grid = (unsigned)(tiles < 1 ? 1 : tiles < RP_MAX_GRID ? tiles : RP_MAX_GRID);      // (src_capacity == 0: K == 0, nothing is read)
   hipLaunchKernelGGL(phx_replay_add_kernel, dim3(grid), dim3(RP_THREADS), 0, st, io->src, io->ring, io->state, io->count_ptr, io->count,
                      io->src_capacity, io->capacity, sh);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_replay_add: the copy: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_replay_add_kernel");
+  if (const int rc = call.launched("the copy", "phx_replay_add_kernel")) return rc;
   hipLaunchKernelGGL(phx_replay_commit_kernel, dim3(1), dim3(64), 0, st, io->state, io->count_ptr, io->count, io->src_capacity, io->capacity);
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_replay_add: the commit: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_replay_commit_kernel");
-  return PHX_OK;
+  return call.launched("the commit", "phx_replay_commit_kernel");
 }
 
 extern "C" int phx_replay_sample(const phx_replay_sample_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_replay_sample: null io");
-  if (io->capacity < 1) return fail(PHX_EINVAL, "phx_replay_sample: capacity = %lld must be >= 1", (long long)io->capacity);
-  if (io->n < 1) return fail(PHX_EINVAL, "phx_replay_sample: n = %lld must be >= 1", (long long)io->n);
-  if (io->row_words < 4 || io->row_words > 256 || (io->row_words & 3))
-    return fail(PHX_EINVAL, "phx_replay_sample: row_words = %d must be a multiple of 4 in [4, 256]", io->row_words);
-  if (io->reserved0 != 0 || io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_replay_sample: reserved must be 0");
-  if (!io->ring || !io->state || !io->out) return fail(PHX_EINVAL, "phx_replay_sample: ring, state and out are required");
-  if (((uintptr_t)io->ring | (uintptr_t)io->state | (uintptr_t)io->out | (uintptr_t)io->out_slot) & 15u)
-    return fail(PHX_EINVAL, "phx_replay_sample: ring, state, out and out_slot must be 16-byte aligned");
-  if ((uintptr_t)io->slot_in & 7u) return fail(PHX_EINVAL, "phx_replay_sample: slot_in must be 8-byte aligned");
+  const char* fn = "phx_replay_sample";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_at_least(fn, "capacity", io->capacity, 1)) return rc;
+  if (const int rc = frag_at_least(fn, "n", io->n, 1)) return rc;
+  if (const int rc = frag_row_words(fn, io->row_words)) return rc;
+  if (const int rc = frag_reserved(fn, io->reserved, io->reserved0)) return rc;
+  if (const int rc = frag_required(fn, io->ring && io->state && io->out, "ring, state and out")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->ring, io->state, io->out, io->out_slot), 16, "ring, state, out and out_slot")) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->slot_in), 8, "slot_in")) return rc;
   const RpShape sh = rp_shape(io->row_words);
-  const int64_t tiles = rp_tiles(io->n, sh);
-  if (tiles < 0) return fail(PHX_EINVAL, "phx_replay_sample: n = %lld is beyond one launch's grid", (long long)io->n);
+  if (const int rc = frag_one_grid(fn, "n", io->n, sh.R)) return rc;
   const uint64_t s0 = rp_mix(rp_mix(io->seed + 0x9E3779B97F4A7C15ull) ^ io->draw);
-  hipLaunchKernelGGL(phx_replay_sample_kernel, dim3((unsigned)tiles), dim3(RP_THREADS), 0, (hipStream_t)stream, io->ring, io->state, io->slot_in,
-                     io->out, io->out_slot, io->n, io->capacity, s0, sh);
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_replay_sample: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_replay_sample_kernel");
-  return PHX_OK;
+  hipLaunchKernelGGL(phx_replay_sample_kernel, dim3((unsigned)rp_tiles(io->n, sh)), dim3(RP_THREADS), 0, (hipStream_t)stream, io->ring, io->state,
+                     io->slot_in, io->out, io->out_slot, io->n, io->capacity, s0, sh);
+  return FragCall{fn}.launched(nullptr, "phx_replay_sample_kernel");
 }

@@ -28,6 +28,7 @@
 
 #include "../../include/phantom_amd_seq.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int SQ_R = 8;              // rows per chunk of the scatter (tests/test_gpu_seq_batch.py walks T and L around it)
 constexpr int SQ_C = 64;             // columns per tile of the scatter: a wave's lanes
@@ -463,94 +464,43 @@ __global__ __launch_bounds__(SQ_THREADS) void phx_seq_scatter_kernel(const phx_s
   sq_pad(a, s, lane, wave);
 }
 
-// phantom_amd_batch.h's six round keys
-static SqKeys sq_keys(const uint64_t seed, const uint64_t epoch) {
-  SqKeys k;
-  uint64_t s = seed ^ (epoch * 0x9E3779B97F4A7C15ull);
-  for (int r = 0; r < 6; ++r) {
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    k.key[r] = (uint32_t)z;
-  }
-  return k;
-}
-
 extern "C" int phx_seq_batch(const phx_seq_batch_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_seq_batch: null io");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_seq_batch: T = %lld and N = %lld must be >= 1", (long long)io->T, (long long)io->N);
-  if (io->T > 0x7fffffffLL) return fail(PHX_EINVAL, "phx_seq_batch: T = %lld must be <= 2^31 - 1", (long long)io->T);
-  if (io->N > (1LL << 62) / io->T) return fail(PHX_EINVAL, "phx_seq_batch: T * N = %lld * %lld must be <= 2^62", (long long)io->T, (long long)io->N);
-  if (io->N > (int64_t)SQ_C * 0x7fffffff) return fail(PHX_EINVAL, "phx_seq_batch: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (io->S < 1 || io->N % io->S != 0) return fail(PHX_EINVAL, "phx_seq_batch: S = %d must be >= 1 and divide N = %lld", io->S, (long long)io->N);
+  const char* fn = "phx_seq_batch";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_batch_shape(fn, *io, SQ_C)) return rc;
   if (io->max_seq_len < 1 || io->max_seq_len > PHX_SEQ_MAX_LEN)
     return fail(PHX_EINVAL, "phx_seq_batch: max_seq_len = %lld must lie in [1, %d]", (long long)io->max_seq_len, PHX_SEQ_MAX_LEN);
-  if (io->n_planes < 0 || io->n_planes > PHX_BATCH_MAX_PLANES)
-    return fail(PHX_EINVAL, "phx_seq_batch: n_planes = %d must lie in [0, %d]", io->n_planes, PHX_BATCH_MAX_PLANES);
-  if (io->row_words < 4 || io->row_words > 256 || (io->row_words & 3))
-    return fail(PHX_EINVAL, "phx_seq_batch: row_words = %d must be a multiple of 4 in [4, 256]", io->row_words);
-  if (io->capacity < 0) return fail(PHX_EINVAL, "phx_seq_batch: capacity = %lld must be >= 0", (long long)io->capacity);
+  if (const int rc = frag_batch_record(fn, *io, PHX_BATCH_MAX_PLANES)) return rc;
   if (io->capacity > (1LL << 62) / io->max_seq_len)
     return fail(PHX_EINVAL, "phx_seq_batch: capacity * max_seq_len = %lld * %lld must be <= 2^62", (long long)io->capacity, (long long)io->max_seq_len);
-  if (io->shuffle != 0 && io->shuffle != 1) return fail(PHX_EINVAL, "phx_seq_batch: shuffle = %d must be 0 or 1", io->shuffle);
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_seq_batch: reserved must be 0");
-  if (!io->seq_start) return fail(PHX_EINVAL, "phx_seq_batch: seq_start is required");
-  if (io->n_planes > 0 && io->capacity > 0 && !io->records) return fail(PHX_EINVAL, "phx_seq_batch: records is required with n_planes > 0");
+  if (const int rc = frag_batch_buffers(fn, *io, io->seq_start, "seq_start")) return rc;
   if ((io->out_col || io->seq_col) && io->N > 0x7fffffffLL)
     return fail(PHX_EINVAL, "phx_seq_batch: out_col and seq_col need N = %lld <= 2^31 - 1", (long long)io->N);
-  bool used[256] = {};
-  for (int k = 0; k < io->n_planes; ++k) {
-    const phx_batch_plane& p = io->plane[k];
-    if (!p.src) return fail(PHX_EINVAL, "phx_seq_batch: plane %d needs src", k);
-    if (p.elem_bytes != 1 && (p.elem_bytes < 4 || p.elem_bytes > 256 || (p.elem_bytes & 3)))
-      return fail(PHX_EINVAL, "phx_seq_batch: plane %d: elem_bytes = %d must be 1 or 4 * w with 1 <= w <= 64", k, p.elem_bytes);
-    if (p.elem_bytes != 1 && ((uintptr_t)p.src & 3u)) return fail(PHX_EINVAL, "phx_seq_batch: plane %d: src must be 4-byte aligned", k);
-    const int w = p.elem_bytes == 1 ? 1 : p.elem_bytes >> 2;
-    if (p.word_off < 0 || p.word_off > io->row_words - w)
-      return fail(PHX_EINVAL, "phx_seq_batch: plane %d: words [%d, %lld) lie outside the record of %d", k, p.word_off, (long long)p.word_off + w,
-                  io->row_words);
-    for (int j = p.word_off; j < p.word_off + w; ++j) {
-      if (used[j]) return fail(PHX_EINVAL, "phx_seq_batch: plane %d overlaps another plane at word %d", k, j);
-      used[j] = true;
-    }
-  }
-  if (io->std_plane < -1 || io->std_plane >= io->n_planes)
-    return fail(PHX_EINVAL, "phx_seq_batch: std_plane = %d must be -1 or a plane index below %d", io->std_plane, io->n_planes);
-  const bool has_std = io->std_plane >= 0;
-  if (has_std && io->plane[io->std_plane].elem_bytes != 4)
-    return fail(PHX_EINVAL, "phx_seq_batch: std_plane = %d must name a plane with elem_bytes 4", io->std_plane);
-  if (has_std && (!io->moments || !io->workspace)) return fail(PHX_EINVAL, "phx_seq_batch: std_plane needs moments and workspace");
-  if (((uintptr_t)io->seq_start | (uintptr_t)io->records | (uintptr_t)io->out_row | (uintptr_t)io->out_col | (uintptr_t)io->moments |
-       (uintptr_t)io->workspace | (uintptr_t)io->seq_lens | (uintptr_t)io->seq_row | (uintptr_t)io->seq_col) & 15u)
-    return fail(PHX_EINVAL, "phx_seq_batch: seq_start, records, out_row, out_col, seq_lens, seq_row, seq_col, moments and workspace must be 16-byte aligned");
+  if (const int rc = frag_batch_planes(fn, *io)) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->seq_start, io->records, io->out_row, io->out_col, io->moments, io->workspace, io->seq_lens,
+                                                io->seq_row, io->seq_col),
+                                  16, "seq_start, records, out_row, out_col, seq_lens, seq_row, seq_col, moments and workspace"))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
+  const bool has_std = io->std_plane >= 0;
   const float* x = has_std ? static_cast<const float*>(io->plane[io->std_plane].src) : nullptr;
   double* sums = static_cast<double*>(io->workspace);                      // [N][2] f64, then the kept rows [N] i64
   int64_t* rows = has_std ? reinterpret_cast<int64_t*>(sums + 2 * io->N) : nullptr;
   hipLaunchKernelGGL(phx_seq_count_kernel, dim3((unsigned)((io->N + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st, io->keep, io->col_class,
                      io->terminated, io->truncated, x, io->seq_start, sums, rows, (int)io->T, io->N, io->S, io->class_id, (int)io->max_seq_len);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_seq_batch: the count: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_seq_count_kernel");
+  if (const int rc = call.launched("the count", "phx_seq_count_kernel")) return rc;
   hipLaunchKernelGGL(phx_seq_scan_kernel, dim3(1), dim3(SS_THREADS), 0, st, io->seq_start, io->N);
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_seq_batch: the scan: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_seq_scan_kernel");
+  if (const int rc = call.launched("the scan", "phx_seq_scan_kernel")) return rc;
   if (has_std) {
     hipLaunchKernelGGL(phx_seq_moments_kernel, dim3(1), dim3(SM_THREADS), 0, st, static_cast<const double*>(sums), static_cast<const int64_t*>(rows),
                        io->moments, io->N);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_seq_batch: the moments: %s", hipGetErrorString(he));
-    phx_note_kernel("phx_seq_moments_kernel");
+    if (const int rc = call.launched("the moments", "phx_seq_moments_kernel")) return rc;
   }
   if (io->capacity == 0 || (!io->records && !io->out_row && !io->out_col && !io->seq_lens && !io->seq_row && !io->seq_col))
     return PHX_OK;                                                         // (nothing to write)
-  hipLaunchKernelGGL(phx_seq_scatter_kernel, dim3((unsigned)((io->N + SQ_C - 1) / SQ_C)), dim3(SQ_THREADS), 0, st, *io, sq_keys(io->seed, io->epoch));
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_seq_batch: the scatter: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_seq_scatter_kernel");
-  return PHX_OK;
+  SqKeys keys;
+  frag_round_keys(io->seed, io->epoch, keys.key);
+  hipLaunchKernelGGL(phx_seq_scatter_kernel, dim3((unsigned)((io->N + SQ_C - 1) / SQ_C)), dim3(SQ_THREADS), 0, st, *io, keys);
+  return call.launched("the scatter", "phx_seq_scatter_kernel");
 }

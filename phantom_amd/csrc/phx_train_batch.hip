@@ -31,6 +31,7 @@
 
 #include "../../include/phantom_amd_batch.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int BT_R = 8;              // rows per chunk of the scatter (tests/test_gpu_train_batch.py walks T around it)
 constexpr int BT_C = 64;             // columns per tile of the scatter: a wave's lanes
@@ -382,87 +383,34 @@ __global__ __launch_bounds__(BT_THREADS) void phx_batch_scatter_kernel(const phx
   }
 }
 
-// the header's six round keys
-static BtKeys bt_keys(const uint64_t seed, const uint64_t epoch) {
-  BtKeys k;
-  uint64_t s = seed ^ (epoch * 0x9E3779B97F4A7C15ull);
-  for (int r = 0; r < 6; ++r) {
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    k.key[r] = (uint32_t)z;
-  }
-  return k;
-}
-
 extern "C" int phx_train_batch(const phx_train_batch_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_train_batch: null io");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_train_batch: T = %lld and N = %lld must be >= 1", (long long)io->T, (long long)io->N);
-  if (io->T > 0x7fffffffLL) return fail(PHX_EINVAL, "phx_train_batch: T = %lld must be <= 2^31 - 1", (long long)io->T);
-  if (io->N > (1LL << 62) / io->T) return fail(PHX_EINVAL, "phx_train_batch: T * N = %lld * %lld must be <= 2^62", (long long)io->T, (long long)io->N);
-  if (io->N > (int64_t)BT_C * 0x7fffffff) return fail(PHX_EINVAL, "phx_train_batch: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (io->S < 1 || io->N % io->S != 0) return fail(PHX_EINVAL, "phx_train_batch: S = %d must be >= 1 and divide N = %lld", io->S, (long long)io->N);
-  if (io->n_planes < 0 || io->n_planes > PHX_BATCH_MAX_PLANES)
-    return fail(PHX_EINVAL, "phx_train_batch: n_planes = %d must lie in [0, %d]", io->n_planes, PHX_BATCH_MAX_PLANES);
-  if (io->row_words < 4 || io->row_words > 256 || (io->row_words & 3))
-    return fail(PHX_EINVAL, "phx_train_batch: row_words = %d must be a multiple of 4 in [4, 256]", io->row_words);
-  if (io->capacity < 0) return fail(PHX_EINVAL, "phx_train_batch: capacity = %lld must be >= 0", (long long)io->capacity);
-  if (io->shuffle != 0 && io->shuffle != 1) return fail(PHX_EINVAL, "phx_train_batch: shuffle = %d must be 0 or 1", io->shuffle);
-  if (io->reserved[0] != 0 || io->reserved[1] != 0) return fail(PHX_EINVAL, "phx_train_batch: reserved must be 0");
-  if (!io->start) return fail(PHX_EINVAL, "phx_train_batch: start is required");
-  if (io->n_planes > 0 && io->capacity > 0 && !io->records) return fail(PHX_EINVAL, "phx_train_batch: records is required with n_planes > 0");
+  const char* fn = "phx_train_batch";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_batch_shape(fn, *io, BT_C)) return rc;
+  if (const int rc = frag_batch_record(fn, *io, PHX_BATCH_MAX_PLANES)) return rc;
+  if (const int rc = frag_batch_buffers(fn, *io, io->start, "start")) return rc;
   if (io->out_col && io->N > 0x7fffffffLL) return fail(PHX_EINVAL, "phx_train_batch: out_col needs N = %lld <= 2^31 - 1", (long long)io->N);
-  bool used[256] = {};
-  for (int k = 0; k < io->n_planes; ++k) {
-    const phx_batch_plane& p = io->plane[k];
-    if (!p.src) return fail(PHX_EINVAL, "phx_train_batch: plane %d needs src", k);
-    if (p.elem_bytes != 1 && (p.elem_bytes < 4 || p.elem_bytes > 256 || (p.elem_bytes & 3)))
-      return fail(PHX_EINVAL, "phx_train_batch: plane %d: elem_bytes = %d must be 1 or 4 * w with 1 <= w <= 64", k, p.elem_bytes);
-    if (p.elem_bytes != 1 && ((uintptr_t)p.src & 3u)) return fail(PHX_EINVAL, "phx_train_batch: plane %d: src must be 4-byte aligned", k);
-    const int w = p.elem_bytes == 1 ? 1 : p.elem_bytes >> 2;
-    if (p.word_off < 0 || p.word_off > io->row_words - w)
-      return fail(PHX_EINVAL, "phx_train_batch: plane %d: words [%d, %lld) lie outside the record of %d", k, p.word_off, (long long)p.word_off + w,
-                  io->row_words);
-    for (int j = p.word_off; j < p.word_off + w; ++j) {
-      if (used[j]) return fail(PHX_EINVAL, "phx_train_batch: plane %d overlaps another plane at word %d", k, j);
-      used[j] = true;
-    }
-  }
-  if (io->std_plane < -1 || io->std_plane >= io->n_planes)
-    return fail(PHX_EINVAL, "phx_train_batch: std_plane = %d must be -1 or a plane index below %d", io->std_plane, io->n_planes);
-  const bool has_std = io->std_plane >= 0;
-  if (has_std && io->plane[io->std_plane].elem_bytes != 4)
-    return fail(PHX_EINVAL, "phx_train_batch: std_plane = %d must name a plane with elem_bytes 4", io->std_plane);
-  if (has_std && (!io->moments || !io->workspace)) return fail(PHX_EINVAL, "phx_train_batch: std_plane needs moments and workspace");
-  if (((uintptr_t)io->start | (uintptr_t)io->records | (uintptr_t)io->out_row | (uintptr_t)io->out_col | (uintptr_t)io->moments |
-       (uintptr_t)io->workspace) & 15u)
-    return fail(PHX_EINVAL, "phx_train_batch: start, records, out_row, out_col, moments and workspace must be 16-byte aligned");
+  if (const int rc = frag_batch_planes(fn, *io)) return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->start, io->records, io->out_row, io->out_col, io->moments, io->workspace), 16,
+                                  "start, records, out_row, out_col, moments and workspace"))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
+  const bool has_std = io->std_plane >= 0;
   const float* x = has_std ? static_cast<const float*>(io->plane[io->std_plane].src) : nullptr;
   hipLaunchKernelGGL(phx_batch_count_kernel, dim3((unsigned)((io->N + BC_THREADS - 1) / BC_THREADS)), dim3(BC_THREADS), 0, st, io->keep, io->col_class,
                      x, io->start, static_cast<double*>(io->workspace), (int)io->T, io->N, io->S, io->class_id);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_train_batch: the count: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_batch_count_kernel");
+  if (const int rc = call.launched("the count", "phx_batch_count_kernel")) return rc;
   hipLaunchKernelGGL(phx_batch_scan_kernel, dim3(1), dim3(BS_THREADS), 0, st, io->start, io->N);
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_train_batch: the scan: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_batch_scan_kernel");
+  if (const int rc = call.launched("the scan", "phx_batch_scan_kernel")) return rc;
   if (has_std) {
     hipLaunchKernelGGL(phx_batch_moments_kernel, dim3(1), dim3(BM_THREADS), 0, st, static_cast<const double*>(io->workspace), io->start, io->moments,
                        io->N);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_train_batch: the moments: %s", hipGetErrorString(he));
-    phx_note_kernel("phx_batch_moments_kernel");
+    if (const int rc = call.launched("the moments", "phx_batch_moments_kernel")) return rc;
   }
   if (io->capacity == 0 || (!io->records && !io->out_row && !io->out_col)) return PHX_OK;      // (nothing to write)
-  hipLaunchKernelGGL(phx_batch_scatter_kernel, dim3((unsigned)((io->N + BT_C - 1) / BT_C)), dim3(BT_THREADS), 0, st, *io,
-                     bt_keys(io->seed, io->epoch));
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_train_batch: the scatter: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_batch_scatter_kernel");
-  return PHX_OK;
+  BtKeys keys;
+  frag_round_keys(io->seed, io->epoch, keys.key);
+  hipLaunchKernelGGL(phx_batch_scatter_kernel, dim3((unsigned)((io->N + BT_C - 1) / BT_C)), dim3(BT_THREADS), 0, st, *io, keys);
+  return call.launched("the scatter", "phx_batch_scatter_kernel");
 }

@@ -28,6 +28,7 @@
 
 #include "../../include/phantom_amd_compact.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int CP_R = 64;             // rows per chunk of the scatter: a wave's lanes (tests/test_gpu_compact.py walks T around it)
 constexpr int CP_C = 64;             // columns per tile of the scatter
@@ -268,44 +269,36 @@ static void cp_launch(const phx_traj_compact_io& io, hipStream_t st) {
 }
 
 extern "C" int phx_traj_compact(const phx_traj_compact_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_traj_compact: null io");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_traj_compact: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)CP_C * 0x7fffffff) return fail(PHX_EINVAL, "phx_traj_compact: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (io->n_planes < 0 || io->n_planes > PHX_COMPACT_MAX_PLANES)
-    return fail(PHX_EINVAL, "phx_traj_compact: n_planes = %d must lie in [0, %d]", io->n_planes, PHX_COMPACT_MAX_PLANES);
-  if (io->capacity < 0) return fail(PHX_EINVAL, "phx_traj_compact: capacity = %lld must be >= 0", (long long)io->capacity);
-  if (!io->keep || !io->start) return fail(PHX_EINVAL, "phx_traj_compact: keep and start are required");
+  const char* fn = "phx_traj_compact";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, CP_C)) return rc;
+  if (const int rc = frag_n_planes(fn, io->n_planes, PHX_COMPACT_MAX_PLANES)) return rc;
+  if (const int rc = frag_at_least(fn, "capacity", io->capacity, 0)) return rc;
+  if (const int rc = frag_required(fn, io->keep && io->start, "keep and start")) return rc;
   if (io->out_col && io->N > 0x7fffffffLL) return fail(PHX_EINVAL, "phx_traj_compact: out_col needs N = %lld <= 2^31 - 1", (long long)io->N);
-  uintptr_t align16 = (uintptr_t)io->start | (uintptr_t)io->out_row | (uintptr_t)io->out_col;
+  uintptr_t align16 = frag_bits(io->start, io->out_row, io->out_col);
   for (int k = 0; k < io->n_planes; ++k) {
     const phx_compact_plane& p = io->plane[k];
     if (!p.src || !p.dst) return fail(PHX_EINVAL, "phx_traj_compact: plane %d needs src and dst", k);
-    if (p.elem_bytes != 1 && (p.elem_bytes < 4 || p.elem_bytes > 256 || (p.elem_bytes & 3)))
-      return fail(PHX_EINVAL, "phx_traj_compact: plane %d: elem_bytes = %d must be 1 or 4 * w with 1 <= w <= 64", k, p.elem_bytes);
+    if (const int rc = frag_plane_elem(fn, k, p.elem_bytes)) return rc;
     if (p.reserved != 0) return fail(PHX_EINVAL, "phx_traj_compact: plane %d: reserved must be 0", k);
-    if (p.elem_bytes != 1 && ((uintptr_t)p.src & 3u)) return fail(PHX_EINVAL, "phx_traj_compact: plane %d: src must be 4-byte aligned", k);
+    if (const int rc = frag_plane_src(fn, k, p.src, p.elem_bytes)) return rc;
     align16 |= (uintptr_t)p.dst;
   }
-  if (align16 & 15u) return fail(PHX_EINVAL, "phx_traj_compact: start, out_row, out_col and every dst must be 16-byte aligned");
+  if (const int rc = frag_aligned(fn, align16, 16, "start, out_row, out_col and every dst")) return rc;
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
   hipLaunchKernelGGL(phx_compact_count_kernel, dim3((unsigned)((io->N + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, st, io->keep, io->start,
                      io->T, io->N);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_traj_compact: the count: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_compact_count_kernel");
+  if (const int rc = call.launched("the count", "phx_compact_count_kernel")) return rc;
   hipLaunchKernelGGL(phx_compact_scan_kernel, dim3(1), dim3(CS_THREADS), 0, st, io->start, io->N);
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_traj_compact: the scan: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_compact_scan_kernel");
+  if (const int rc = call.launched("the scan", "phx_compact_scan_kernel")) return rc;
   if (io->capacity == 0 || (io->n_planes == 0 && !io->out_row && !io->out_col)) return PHX_OK;      // (nothing to write)
   if (io->out_row) {
     if (io->out_col) cp_launch<true, true>(*io, st); else cp_launch<true, false>(*io, st);
   } else {
     if (io->out_col) cp_launch<false, true>(*io, st); else cp_launch<false, false>(*io, st);
   }
-  he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_traj_compact: the scatter: %s", hipGetErrorString(he));
-  phx_note_kernel("phx_compact_scatter_kernel");
-  return PHX_OK;
+  return call.launched("the scatter", "phx_compact_scatter_kernel");
 }

@@ -31,6 +31,7 @@
 
 #include "../../include/phantom_amd_traj.h"
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int TN_K = 8;            // rows per chunk (tests/test_gpu_traj_next.py walks T below, at and across it)
 constexpr int TN_LANES = 64;       // columns per workgroup: one wave
@@ -198,32 +199,30 @@ static void tg_launch(const phx_traj_next_io& io, hipStream_t st) {
 }
 
 extern "C" int phx_traj_next(const phx_traj_next_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_traj_next: null io");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_traj_next: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)TN_LANES * 0x7fffffff) return fail(PHX_EINVAL, "phx_traj_next: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (!io->truncated || !io->next_row || !io->next_terminated || !io->next_truncated)
-    return fail(PHX_EINVAL, "phx_traj_next: truncated, next_row, next_terminated and next_truncated are required");
+  const char* fn = "phx_traj_next";
+  if (const int rc = frag_io(fn, io)) return rc;
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, TN_LANES)) return rc;
+  if (const int rc = frag_required(fn, io->truncated && io->next_row && io->next_terminated && io->next_truncated,
+                                   "truncated, next_row, next_terminated and next_truncated"))
+    return rc;
   if (io->next_obs) {
     if (!io->obs || !io->new_obs) return fail(PHX_EINVAL, "phx_traj_next: next_obs needs both obs and new_obs");
     if (io->D < 1 || io->D > 64) return fail(PHX_EINVAL, "phx_traj_next: D = %d must lie in [1, 64] when next_obs is given", io->D);
-    if (io->N * io->D > (int64_t)TG_THREADS * 0x7fffffff)
-      return fail(PHX_EINVAL, "phx_traj_next: N = %lld with D = %d is beyond one launch's grid", (long long)io->N, io->D);
-    if (((uintptr_t)io->obs | (uintptr_t)io->new_obs) & 3u) return fail(PHX_EINVAL, "phx_traj_next: obs and new_obs must be 4-byte aligned");
+    if (io->N * io->D > (int64_t)TG_THREADS * 0x7fffffff) return frag_beyond_grid(fn, "N = %lld with D = %d is", (long long)io->N, io->D);
+    if (const int rc = frag_aligned(fn, frag_bits(io->obs, io->new_obs), 4, "obs and new_obs")) return rc;
   }
-  if (((uintptr_t)io->next_row | (uintptr_t)io->next_terminated | (uintptr_t)io->next_truncated | (uintptr_t)io->next_obs) & 15u)
-    return fail(PHX_EINVAL, "phx_traj_next: next_row, next_terminated, next_truncated and next_obs must be 16-byte aligned");
+  if (const int rc = frag_aligned(fn, frag_bits(io->next_row, io->next_terminated, io->next_truncated, io->next_obs), 16,
+                                  "next_row, next_terminated, next_truncated and next_obs"))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
+  FragCall call{fn};
   const int which = (io->terminated ? 4 : 0) | (io->acted ? 2 : 0) | (io->new_obs_valid ? 1 : 0);
   tn_launch<7>(which, *io, st);
-  hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_traj_next: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_traj_next_kernel");
+  if (const int rc = call.launched(nullptr, "phx_traj_next_kernel")) return rc;
   if (io->next_obs) {
     if (io->N * io->D <= 0xffffff00LL) tg_launch<uint32_t>(*io, st); else tg_launch<uint64_t>(*io, st);
-    he = hipGetLastError();
-    if (he != hipSuccess) return fail(PHX_EHIP, "phx_traj_next: the gather: %s", hipGetErrorString(he));
-    phx_note_kernel("phx_traj_gather_kernel");
+    if (const int rc = call.launched("the gather", "phx_traj_gather_kernel")) return rc;
   }
   return PHX_OK;
 }

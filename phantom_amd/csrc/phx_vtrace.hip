@@ -29,6 +29,7 @@
 #include "../../include/phantom_amd_vtrace.h"
 #include "phx_sc_policy.h"         // pol_exp: the PHX_EXP_* procedure of phantom_amd.h (device inlines only, no kernel)
 #include "phx_spec.h"
+#include "phx_frag.h"
 
 constexpr int VT_K = 8;            // rows per chunk (tests/test_gpu_vtrace.py walks T below, at and across it)
 constexpr int VT_LANES = 64;       // columns per workgroup: one wave
@@ -169,20 +170,22 @@ static void vt_launch(const phx_vtrace_io& io, hipStream_t st) {
 static bool vt_threshold_ok(const float x) { return x > 0.0f && x <= 3.402823466e+38f; }      // finite and > 0 (NaN fails both)
 
 extern "C" int phx_vtrace(const phx_vtrace_io* io, void* stream) {
-  if (!io) return fail(PHX_EINVAL, "phx_vtrace: null io");
+  const char* fn = "phx_vtrace";
+  if (const int rc = frag_io(fn, io)) return rc;
   if (io->reserved0 != 0 || !(io->reserved1 == 0.0f)) return fail(PHX_EINVAL, "phx_vtrace: reserved0 and reserved1 must be 0");
-  if (io->T < 1 || io->N < 1) return fail(PHX_EINVAL, "phx_vtrace: T = %d and N = %lld must be >= 1", io->T, (long long)io->N);
-  if (io->N > (int64_t)VT_LANES * 0x7fffffff) return fail(PHX_EINVAL, "phx_vtrace: N = %lld is beyond one launch's grid", (long long)io->N);
-  if (!(io->gamma >= 0.0f && io->gamma <= 1.0f) || !(io->lambda >= 0.0f && io->lambda <= 1.0f))
-    return fail(PHX_EINVAL, "phx_vtrace: gamma = %g and lambda = %g must lie in [0, 1]", (double)io->gamma, (double)io->lambda);
+  if (const int rc = frag_rows_cols(fn, io->T, io->N)) return rc;
+  if (const int rc = frag_one_grid(fn, "N", io->N, VT_LANES)) return rc;
+  if (const int rc = frag_gamma_lambda(fn, io->gamma, io->lambda)) return rc;
   if (!vt_threshold_ok(io->rho_bar) || !vt_threshold_ok(io->c_bar) || !vt_threshold_ok(io->pg_rho_bar))
     return fail(PHX_EINVAL, "phx_vtrace: rho_bar = %g, c_bar = %g and pg_rho_bar = %g must be finite and > 0", (double)io->rho_bar,
                 (double)io->c_bar, (double)io->pg_rho_bar);
-  if (!io->reward || !io->vf_pred || !io->behaviour_logp || !io->target_logp || !io->truncated || !io->vs)
-    return fail(PHX_EINVAL, "phx_vtrace: reward, vf_pred, behaviour_logp, target_logp, truncated and vs are required");
-  if (((uintptr_t)io->reward | (uintptr_t)io->vf_pred | (uintptr_t)io->vf_next | (uintptr_t)io->behaviour_logp | (uintptr_t)io->target_logp) & 3u)
-    return fail(PHX_EINVAL, "phx_vtrace: reward, vf_pred, vf_next, behaviour_logp and target_logp must be 4-byte aligned");
-  if (((uintptr_t)io->vs | (uintptr_t)io->pg_advantage) & 15u) return fail(PHX_EINVAL, "phx_vtrace: vs and pg_advantage must be 16-byte aligned");
+  if (const int rc = frag_required(fn, io->reward && io->vf_pred && io->behaviour_logp && io->target_logp && io->truncated && io->vs,
+                                   "reward, vf_pred, behaviour_logp, target_logp, truncated and vs"))
+    return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->reward, io->vf_pred, io->vf_next, io->behaviour_logp, io->target_logp), 4,
+                                  "reward, vf_pred, vf_next, behaviour_logp and target_logp"))
+    return rc;
+  if (const int rc = frag_aligned(fn, frag_bits(io->vs, io->pg_advantage), 16, "vs and pg_advantage")) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const int which = (io->vf_next ? 2 : 0) | (io->terminated ? 1 : 0);
   switch (which) {
@@ -191,9 +194,5 @@ extern "C" int phx_vtrace(const phx_vtrace_io* io, void* stream) {
     case 2: vt_launch<true, false>(*io, st); break;
     default: vt_launch<true, true>(*io, st); break;
   }
-  const hipError_t he = hipGetLastError();
-  if (he != hipSuccess) return fail(PHX_EHIP, "phx_vtrace: %s", hipGetErrorString(he));
-  phx_note_reset();
-  phx_note_kernel("phx_vtrace_kernel");
-  return PHX_OK;
+  return FragCall{fn}.launched(nullptr, "phx_vtrace_kernel");
 }

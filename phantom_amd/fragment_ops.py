@@ -69,6 +69,25 @@ def _capacity(fn, capacity, default) -> int:
     return capacity
 
 
+def _count(fn, count, src_capacity, device):
+    """``(count_ptr, host_count)`` of an add's ``count``: None for all ``src_capacity`` records, an int in ``[0, src_capacity]`` or a
+    device i64 tensor of one element"""
+    if count is None:
+        return None, src_capacity
+    if hasattr(count, "dim"):
+        if count.numel() != 1:
+            raise ValueError(f"{fn}: a device `count` must hold one element, got shape {tuple(count.shape)}")
+        check_tensor(fn, "count", count, _torch().int64, tuple(count.shape), align=8, device=device)
+        return count, 0
+    return None, _int(fn, "count", count, 0, src_capacity, f"None, a device i64 tensor or an int in [0, {src_capacity}]")
+
+
+def _draws(fn, n, seed, draw):
+    """``(n, seed, draw)`` of a sampling call: n >= 1 draws of the stream ``(seed, draw)``"""
+    return (_int(fn, "n", n, 1), _int(fn, "seed", seed, 0, 2 ** 64 - 1, "an int in [0, 2^64)"),
+            _int(fn, "draw", draw, 0, 2 ** 64 - 1, "an int in [0, 2^64)"))
+
+
 def _set_batch_planes(io, planes, layout):
     for k, (name, x) in enumerate(planes.items()):
         io.plane[k] = _abi.PhxBatchPlane(src=_ptr(x), elem_bytes=x.element_size() * layout[name][1], word_off=layout[name][0])
@@ -533,16 +552,7 @@ class FragmentOps:
             raise ValueError(f"replay_add: `records` must be an i32 [src_capacity, {row_words}] tensor")
         src_capacity = int(records.shape[0])
         check_tensor("replay_add", "records", records, torch.int32, (src_capacity, row_words), align=16, device=self.device)
-        count_ptr, host_count = None, 0
-        if count is None:
-            host_count = src_capacity
-        elif hasattr(count, "dim"):
-            if count.numel() != 1:
-                raise ValueError(f"replay_add: a device `count` must hold one element, got shape {tuple(count.shape)}")
-            check_tensor("replay_add", "count", count, torch.int64, tuple(count.shape), align=8, device=self.device)
-            count_ptr = count
-        else:
-            host_count = _int("replay_add", "count", count, 0, src_capacity, f"None, a device i64 tensor or an int in [0, {src_capacity}]")
+        count_ptr, host_count = _count("replay_add", count, src_capacity, self.device)
         self._launch("phx_replay_add", _abi.PhxReplayAddIO(
             capacity=Cn, src_capacity=src_capacity, count=host_count, row_words=row_words, count_ptr=_ptr(count_ptr),
             src=_ptr(records) if src_capacity else None, ring=_ptr(ring), state=_ptr(state)))
@@ -556,9 +566,7 @@ class FragmentOps:
         caller-owned and 16-byte aligned; allocated here when None.  The call does not synchronise."""
         torch = _torch()
         Cn, row_words = self._replay_ring("replay_sample", ring, state)
-        n = _int("replay_sample", "n", n, 1)
-        seed = _int("replay_sample", "seed", seed, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
-        draw = _int("replay_sample", "draw", draw, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
+        n, seed, draw = _draws("replay_sample", n, seed, draw)
         if slots is not None:
             check_tensor("replay_sample", "slots", slots, torch.int64, (n,), align=8, device=self.device)
         rec, oslot = self._outputs("replay_sample", out, ((torch.int32, (n, row_words), REQUIRED), (torch.int64, (n,), OPTIONAL)),
@@ -587,19 +595,9 @@ class FragmentOps:
         is the ring's i64 ``[4]`` state, read only -- the call comes BEFORE the ring's add.  ``src_capacity`` and ``count`` are the
         ring add's: the records the batch's buffer holds, and None for all of them, an int K in ``[0, src_capacity]`` or a device i64
         tensor of one element that holds K.  A K outside ``[0, src_capacity]`` changes nothing and counts in the state's ``refused``."""
-        torch = _torch()
         Cn = self._prio_tree("prio_add", tree, pstate, ring_state, capacity)
         src_capacity = _int("prio_add", "src_capacity", src_capacity, 0)
-        count_ptr, host_count = None, 0
-        if count is None:
-            host_count = src_capacity
-        elif hasattr(count, "dim"):
-            if count.numel() != 1:
-                raise ValueError(f"prio_add: a device `count` must hold one element, got shape {tuple(count.shape)}")
-            check_tensor("prio_add", "count", count, torch.int64, tuple(count.shape), align=8, device=self.device)
-            count_ptr = count
-        else:
-            host_count = _int("prio_add", "count", count, 0, src_capacity, f"None, a device i64 tensor or an int in [0, {src_capacity}]")
+        count_ptr, host_count = _count("prio_add", count, src_capacity, self.device)
         self._launch("phx_prio_add", _abi.PhxPrioAddIO(
             capacity=Cn, src_capacity=src_capacity, count=host_count, count_ptr=_ptr(count_ptr), ring_state=_ptr(ring_state), tree=_ptr(tree),
             state=_ptr(pstate)))
@@ -627,9 +625,7 @@ class FragmentOps:
         16-byte aligned; allocated here when None.  The call does not synchronise."""
         torch = _torch()
         Cn = self._prio_tree("prio_sample", tree, pstate, ring_state, capacity)
-        n = _int("prio_sample", "n", n, 1)
-        seed = _int("prio_sample", "seed", seed, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
-        draw = _int("prio_sample", "draw", draw, 0, 2 ** 64 - 1, "an int in [0, 2^64)")
+        n, seed, draw = _draws("prio_sample", n, seed, draw)
         oslot, oprio = self._outputs("prio_sample", out, ((torch.int64, (n,), REQUIRED), (torch.float32, (n,), REQUIRED)), "(out_slot, out_priority)")
         self._launch("phx_prio_sample", _abi.PhxPrioSampleIO(
             capacity=Cn, n=n, seed=seed, draw=draw, ring_state=_ptr(ring_state), tree=_ptr(tree), out_slot=_ptr(oslot), out_priority=_ptr(oprio)))

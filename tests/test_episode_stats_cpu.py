@@ -282,7 +282,8 @@ def test_struct_symbol_headers_and_build_lists():
     assert "phx_episode_stats" not in _abi.EXPORTS and _abi.ABI_VERSION == 10
     assert (_abi.EPISODE_SCAN_KERNEL, _abi.EPISODE_REDUCE_KERNEL) == ("phx_episode_scan_kernel", "phx_episode_reduce_kernel")
     for name in (_abi.EPISODE_SCAN_KERNEL, _abi.EPISODE_REDUCE_KERNEL):
-        assert f'phx_note_kernel("{name}")' in SRC
+        assert re.search(rf'\.launched\("[^"\n]*", "{name}"\)', SRC)      # (FragCall::launched of phx_frag.h notes the name)
+    assert "phx_note_kernel(kernel);" in open(os.path.join(build.CSRC, "phx_frag.h")).read()
     assert int(re.search(r"constexpr int EP_MAX_G = (\d+);", SRC).group(1)) == _abi.EPISODE_MAX_G == 256
     assert int(re.search(r"constexpr int EP_RED = (\d+);", SRC).group(1)) == er.LANES == 256
     assert re.search(r"constexpr int EP_K = (\d+);", SRC) and re.search(r"constexpr int EP_LANES = (\d+);", SRC)

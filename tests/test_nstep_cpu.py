@@ -202,7 +202,8 @@ def test_struct_symbol_headers_and_build_lists():
                                                                                          "phx_nstep_gather_kernel")
     src = open(os.path.join(build.CSRC, "phx_nstep.hip")).read()
     for name in (_abi.NSTEP_SUCC_KERNEL, _abi.NSTEP_FOLD_KERNEL, _abi.NSTEP_GATHER_KERNEL):
-        assert f'phx_note_kernel("{name}")' in src
+        assert re.search(rf'\.launched\("[^"\n]*", "{name}"\)', src)      # (FragCall::launched of phx_frag.h notes the name)
+    assert "phx_note_kernel(kernel);" in open(os.path.join(build.CSRC, "phx_frag.h")).read()
     assert int(re.search(r"constexpr int NSTEP_MAX_N = (\d+);", src).group(1)) == _abi.NSTEP_MAX_N == 64
     assert "phx_nstep.hip" in build.SOURCES and any(h.endswith("phantom_amd_nstep.h") for h in build.HEADERS)
     assert all(os.path.exists(os.path.join(build.CSRC, f)) for f in build.SOURCES + build.HEADERS)
